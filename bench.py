@@ -12,15 +12,21 @@ ranks hold ONE global batch of N x 2^20 packets: rank s owns packets [s 2^20, (s
 index g -> pn 0x10000000 + g, key row g mod K, payload bytes [1200 g, 1200 (g+1)) of the SplitMix64
 stream). Rank 0 derives the keys and broadcasts them (RCCL); packets are independent, so there is
 no data-path collective ("weak" scaling). After the timed region the ranks all-reduce their
-failure counts and tag checksums; rank 0 checks the checksum of a fixed sample of global indices
-against the CPU oracle (the checker, outside the timed region).
+failure counts and, with --full, their tag checksums; rank 0 then checks the checksum of a fixed
+sample of global indices against the CPU oracle (the checker, outside the timed region).
+
+A plain run sets up, warms up, times the steps, gates `value` on the statuses and packet numbers
+the steps returned, and prints the result line. --full adds the oracle parity and the CPU baselines;
+--dump-outputs DIR writes what the last step left as DIR/<name>.npy (dump_outputs below), the
+inputs being the same for the same arguments.
 
   value  = sum over ranks of wire bytes x 2 / max-over-ranks(t_seal + t_open) / 2^30   [GiB/s]
   roofline.achieved = algorithmic bytes of one seal (2 x L per packet: read + write) / the seal
                       composite's average duration (tile kernel + HP pass), HIP events on its stream
-  cpu_baseline = the C oracle (oracle/, "port") on a bounded sample (1 core, the box's CPU share,
-                 all cores); cpu_openssl = OpenSSL EVP running the same composites
+  cpu_baseline = (--full) the C oracle (oracle/, "port") on a bounded sample (1 core, the box's CPU
+                 share, all cores); cpu_openssl = OpenSSL EVP running the same composites
 Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--config b|c|e] [--packets P] [--keys K]
+                       [--full [--no-cpu-baseline]] [--dump-outputs DIR] [--e2e]
 """
 import argparse
 import json
@@ -49,7 +55,13 @@ def parse(argv=None):
     ap.add_argument("--config", default="b", choices=["b", "c", "e"])
     ap.add_argument("--packets", type=int, default=1 << 20, help="packets per GPU")
     ap.add_argument("--keys", type=int, default=1, help="configs b/c: key rows, key_id = g mod K (SURVEY §8d)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run what the headline figure does not need: the tag-checksum "
+                         "parity against the CPU oracle and the CPU baselines (port and OpenSSL)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last step left (statuses, packet numbers, the bytes "
+                         "of a fixed sample of packets) as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
     ap.add_argument("--cpu-sample", type=int, default=1 << 16, help="packets in the CPU baseline sample")
     ap.add_argument("--cpu-seconds", type=float, default=8.0, help="minimum timed CPU work per thread count")
     ap.add_argument("--e2e", action="store_true", help="also measure the host-resident (H2D+D2H) rate")
@@ -129,14 +141,19 @@ def sample_for_rank(n_global, first, n_local):
     return g, mine - first
 
 
-def parity_check(cfg, n_global, g_sample, keys, fails, csum, s_csum, pn_ok, dist=None, device=None):
+def parity_check(cfg, n_global, g_sample, keys, fails, csum, s_csum, pn_ok, dist=None, device=None, oracle=True):
     """Whole-job parity after the timed region (the checker, CPU oracle). Every config holds ONE
     global batch: the ranks all-reduce the checksum of the tags at the fixed global sample and
     rank 0's oracle seals exactly those packets. Returns the parity record (identical on every
-    rank)."""
+    rank). oracle=False (a run without --full): only the statuses and packet numbers the steps
+    themselves returned are reduced; csum and s_csum are not looked at."""
     from milli_quic_amd import shard
     world = dist.get_world_size() if dist is not None and dist.is_initialized() else 1
     rank = dist.get_rank() if world > 1 else 0
+    if not oracle:
+        fails_all, pn_bad = shard.reduce_sums([fails, 0 if pn_ok else 1], dist, device)
+        return {"failures": fails_all, "pn_mismatch_ranks": pn_bad, "oracle": "not run (--full runs it)",
+                "match": bool(fails_all == 0 and pn_bad == 0)}
     fails_all, csum_all, s_csum_all, pn_bad = shard.reduce_sums(
         [fails, csum, s_csum, 0 if pn_ok else 1], dist, device)
     o_fail, o_csum = oracle_sample_checksum(cfg, n_global, g_sample, keys) if rank == 0 else (0, None)
@@ -422,6 +439,43 @@ def load_traffic(cfg, kerns, keys=1):
         return None
 
 
+# ---- --dump-outputs ---------------------------------------------------------------------------
+DUMP_SAMPLE = 8192  # packets whose bytes are written: at most 8192 x 1350 B x 4 (float32) = 44 MB
+
+
+def dump_sample(n, count=DUMP_SAMPLE):
+    """The fixed sample of local packet positions --dump-outputs writes the bytes of: `count`
+    positions drawn without replacement by a seeded generator, sorted (all of them if n <= count)."""
+    if n <= count:
+        return np.arange(n, dtype=np.int64)
+    return np.sort(np.random.Generator(np.random.PCG64(0x6D71)).choice(n, size=count, replace=False)).astype(np.int64)
+
+
+def dump_outputs(path, torch, w, arena, st, pn, rank=0, world=1):
+    """What a caller of the timed path holds after its last step (seal, then open, in place), as
+    float arrays two builds can be compared by:
+      status.npy        float32 [n]  per-packet status of the last open (0 = MQ_OK)
+      pn.npy            float64 [n]  packet numbers the last open decoded (exact below 2^53)
+      sample_index.npy  float64 [m]  positions in the batch of the sampled packets
+      sample_bytes.npy  float32 [sum of the sampled lengths]  those packets' bytes in the arena, in
+                        order: header with protection removed, plaintext, the tag the last seal wrote
+    About 57 MB at most (12 MB for status and pn of 2^20 packets, 44 MB of sample bytes). Ranks of
+    an N-GPU run write <name>.rank<r>.npy."""
+    os.makedirs(path, exist_ok=True)
+    pos = dump_sample(w.n)
+    offs = w.seal_desc["offset"].astype(np.int64)[pos]
+    lens = w.seal_desc["len"].astype(np.int64)[pos]
+    starts = np.cumsum(lens) - lens  # where each sampled packet begins in the output
+    idx = np.repeat(offs - starts, lens) + np.arange(int(lens.sum()), dtype=np.int64)
+    sample = arena[torch.from_numpy(idx).to(arena.device)].cpu().numpy()
+    suffix = "" if world == 1 else f".rank{rank}"
+    for name, a in (("status", st.cpu().numpy().astype(np.float32)),
+                    ("pn", pn.cpu().numpy().view(np.uint64).astype(np.float64)),
+                    ("sample_index", pos.astype(np.float64)),
+                    ("sample_bytes", sample.astype(np.float32))):
+        np.save(os.path.join(path, name + suffix + ".npy"), a)
+
+
 def main():
     args = parse()
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
@@ -508,16 +562,22 @@ def main():
     seal_ms, open_ms = float(seal_t.mean()), float(open_t.mean())
     pn_ok = bool((pn.cpu().numpy().view(np.uint64) == w.pns).all())
 
-    # cross-rank parity: after the steps every packet holds its plaintext and the tag the last seal
-    # wrote; all-reduce failures and tag checksums (whole shard, and the fixed global sample)
-    offs_t = torch.from_numpy(w.seal_desc["offset"].astype(np.int64)).to(dev)
-    lens_t = torch.from_numpy(w.seal_desc["len"].astype(np.int64)).to(dev)
-    g_sample, local_sample = sample_for_rank(args.packets * world, first, w.n)
-    ls = torch.from_numpy(local_sample.astype(np.int64)).to(dev)
-    csum = shard.tag_checksum_torch(arena, offs_t, lens_t)
-    s_csum = shard.tag_checksum_torch(arena, offs_t[ls], lens_t[ls])
-    parity = parity_check(args.config, args.packets * world, g_sample, keys, fails, csum, s_csum, pn_ok, dd, dev)
+    if args.full:
+        # cross-rank parity: after the steps every packet holds its plaintext and the tag the last seal
+        # wrote; all-reduce failures and tag checksums (whole shard, and the fixed global sample)
+        offs_t = torch.from_numpy(w.seal_desc["offset"].astype(np.int64)).to(dev)
+        lens_t = torch.from_numpy(w.seal_desc["len"].astype(np.int64)).to(dev)
+        g_sample, local_sample = sample_for_rank(args.packets * world, first, w.n)
+        ls = torch.from_numpy(local_sample.astype(np.int64)).to(dev)
+        csum = shard.tag_checksum_torch(arena, offs_t, lens_t)
+        s_csum = shard.tag_checksum_torch(arena, offs_t[ls], lens_t[ls])
+        parity = parity_check(args.config, args.packets * world, g_sample, keys, fails, csum, s_csum, pn_ok, dd, dev)
+    else:  # only what the steps themselves returned: every status MQ_OK, every packet number right
+        parity = parity_check(args.config, args.packets * world, None, keys, fails, 0, 0, pn_ok, dd, dev,
+                              oracle=False)
     fails_all = parity["failures"]
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, torch, w, arena, st, pn, rank, world)
 
     wire = w.wire_bytes
     tot = shard.reduce_totals(elapsed, wire, 0, dd, dev)
@@ -548,7 +608,7 @@ def main():
                 # host time to enqueue each of the first timed steps (ms): a slow enqueue idles the GPU
                 "host_enqueue_ms_first5": [round((b - a) * 1e3, 3) for a, b in zip([t0] + host_t[:4], host_t[:5])]}
         cpu = ossl = None
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             cpu = cpu_baseline(w, args.cpu_sample, args.cpu_seconds)
             ossl = cpu_openssl(w, args.cpu_sample)
         names = {"b": "configs[1]: 1M x 1200B ChaCha20-Poly1305 seal+open, 1-RTT short header",

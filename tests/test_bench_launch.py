@@ -122,3 +122,47 @@ def test_roofline_seal_composite_traffic():
         with open(os.path.join(HERE, "..", "profiles", f"pmc_traffic_{cfg}.json")) as f:
             d = {k.split("(")[0]: v["hbm_bytes_per_launch"] for k, v in json.load(f)["kernels"].items()}
         assert bench.load_traffic(cfg, ks) == int(sum(d[k] for k in ks))
+
+
+def test_plain_run_options():
+    """--full and --dump-outputs are off by default; a run without --full gates on the statuses and
+    packet numbers alone and never calls the oracle (g_sample and the checksums are not read)."""
+    a = bench.parse(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert (a.full, a.dump_outputs, a.steps, a.warmup) == (False, None, 7, 2)
+    a = bench.parse(["--full", "--dump-outputs", "d"])
+    assert a.full and a.dump_outputs == "d"
+    p = bench.parity_check("b", 64, None, None, 0, None, None, True, oracle=False)
+    assert p["match"] and p["failures"] == 0 and p["pn_mismatch_ranks"] == 0
+    assert not bench.parity_check("b", 64, None, None, 3, None, None, True, oracle=False)["match"]
+    assert not bench.parity_check("b", 64, None, None, 0, None, None, False, oracle=False)["match"]
+
+
+def test_dump_outputs_fixed_sample(tmp_path):
+    """--dump-outputs: float .npy arrays of the statuses, packet numbers and the bytes of a fixed
+    (seeded) sample of packets, identical from call to call, within the 64 MB the option allows
+    at the bench's full size."""
+    import torch
+    pos = bench.dump_sample(1 << 20)
+    assert len(pos) == bench.DUMP_SAMPLE == len(np.unique(pos)) and (np.diff(pos) > 0).all()
+    assert pos[0] >= 0 and pos[-1] < 1 << 20 and (pos == bench.dump_sample(1 << 20)).all()
+    assert (bench.dump_sample(100) == np.arange(100)).all()
+    assert (1 << 20) * (4 + 8) + bench.DUMP_SAMPLE * (8 + 1350 * 4) <= 64 * 10 ** 6
+    # mixed lengths, more packets than the sample: the gathered bytes are those packets' bytes
+    w = workload.config_e(bench.DUMP_SAMPLE + 500)
+    arena = torch.from_numpy(w.arena.copy())
+    st = torch.zeros(w.n, dtype=torch.uint8)
+    st[5] = 1
+    pn = torch.from_numpy(w.pns.view(np.int64).copy())
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), torch, w, arena, st, pn)
+    got = {f: np.load(tmp_path / "a" / f) for f in sorted(os.listdir(tmp_path / "a"))}
+    assert sorted(got) == ["pn.npy", "sample_bytes.npy", "sample_index.npy", "status.npy"]
+    assert all(a.dtype in (np.float32, np.float64) for a in got.values())
+    for f, a in got.items():
+        assert (a == np.load(tmp_path / "b" / f)).all()
+    idx = got["sample_index.npy"].astype(np.int64)
+    assert (idx == bench.dump_sample(w.n)).all() and len(idx) == bench.DUMP_SAMPLE
+    assert (got["status.npy"] == st.numpy()).all() and (got["pn.npy"] == w.pns.astype(np.float64)).all()
+    want = np.concatenate([w.arena[int(o):int(o) + int(ln)]
+                           for o, ln in zip(w.seal_desc["offset"][idx], w.seal_desc["len"][idx])])
+    assert got["sample_bytes.npy"].shape == want.shape and (got["sample_bytes.npy"] == want).all()

@@ -12,23 +12,23 @@ step tests
 timeout -k 10 900 python -u -m pytest tests -m gpu -x -v --timeout 300 --timeout-method thread > $O/tests.log 2>&1 || { tail -30 $O/tests.log; exit 1; }
 tail -2 $O/tests.log
 step bench_b
-timeout -k 10 400 python bench.py > $O/bench_b.json 2> $O/bench_b.err || { tail $O/bench_b.err; exit 1; }
+timeout -k 10 400 python bench.py --full > $O/bench_b.json 2> $O/bench_b.err || { tail $O/bench_b.err; exit 1; }
 cat $O/bench_b.json
 step bench_b_e2e
-timeout -k 10 600 python bench.py --no-cpu-baseline --e2e > $O/bench_b_e2e.json 2> $O/bench_b_e2e.err || { tail $O/bench_b_e2e.err; exit 1; }
+timeout -k 10 600 python bench.py --full --no-cpu-baseline --e2e > $O/bench_b_e2e.json 2> $O/bench_b_e2e.err || { tail $O/bench_b_e2e.err; exit 1; }
 cat $O/bench_b_e2e.json
 for c in c e; do
   step bench_$c
-  timeout -k 10 300 python bench.py --config $c --no-cpu-baseline > $O/bench_$c.json 2> $O/bench_$c.err || { tail $O/bench_$c.err; exit 1; }
+  timeout -k 10 300 python bench.py --full --config $c --no-cpu-baseline > $O/bench_$c.json 2> $O/bench_$c.err || { tail $O/bench_$c.err; exit 1; }
   cat $O/bench_$c.json
 done
 for c in b c; do
   step bench_${c}_k1024
-  timeout -k 10 300 python bench.py --config $c --keys 1024 --no-cpu-baseline > $O/bench_${c}_k1024.json 2> $O/bench_${c}_k1024.err || { tail $O/bench_${c}_k1024.err; exit 1; }
+  timeout -k 10 300 python bench.py --full --config $c --keys 1024 --no-cpu-baseline > $O/bench_${c}_k1024.json 2> $O/bench_${c}_k1024.err || { tail $O/bench_${c}_k1024.err; exit 1; }
   cat $O/bench_${c}_k1024.json
 done
 step gloo_2rank
-MQ_BENCH_BACKEND=gloo timeout -k 10 400 python bench.py --gpus 2 --no-cpu-baseline > $O/bench_b_2rank_gloo.json 2> $O/bench_b_2rank_gloo.err || { tail $O/bench_b_2rank_gloo.err; exit 1; }
+MQ_BENCH_BACKEND=gloo timeout -k 10 400 python bench.py --full --gpus 2 --no-cpu-baseline > $O/bench_b_2rank_gloo.json 2> $O/bench_b_2rank_gloo.err || { tail $O/bench_b_2rank_gloo.err; exit 1; }
 cat $O/bench_b_2rank_gloo.json
 step latency
 timeout -k 10 300 python tools/bench_latency.py > $O/latency.json 2> $O/latency.err || { tail $O/latency.err; exit 1; }
