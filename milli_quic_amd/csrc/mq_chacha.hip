@@ -1016,7 +1016,10 @@ __device__ __forceinline__ void chacha_narrow_list(uint8_t* wsm, uint32_t u, con
 // LIST: a partition list with narrow regions (reg): the octet tiles are the G = 8 region's (count =
 // its entries), a workgroup with an octet tile runs the pool's barriers on every wave (its narrow
 // waves run their tile first), one without any runs its narrow tiles with no barrier.
-template <bool OPEN, bool SINGLE, bool LIST = false, uint32_t IMG = kLdsBytes, uint32_t W = kCcWaves>
+// n_rows carries the MQ_CC_SPAN=0 switch in its top bit (a key table never has 2^31 rows).
+constexpr uint32_t kCcNoSpan = 0x80000000u;
+// SPAN = false: no span tiles in this kernel, whatever the switch says (chacha_list).
+template <bool OPEN, bool SINGLE, bool LIST = false, uint32_t IMG = kLdsBytes, uint32_t W = kCcWaves, bool SPAN = true>
 __device__ __forceinline__ void chacha_tile(uint32_t tb, uint32_t tid, const KeyRow* __restrict__ kt, uint32_t n_rows,
                                             uint8_t* __restrict__ arena, uint64_t arena_len,
                                             const mq_pkt_desc* __restrict__ desc, uint32_t n,
@@ -1028,6 +1031,8 @@ __device__ __forceinline__ void chacha_tile(uint32_t tb, uint32_t tid, const Key
   uint8_t* wsm = smem + w * IMG;
   const int lane = tid & (kWave - 1), p = lane / kLanesPerPkt, j = lane % kLanesPerPkt;
   const uint32_t tile_id = tb * W + w;
+  const bool span_ok = SPAN && (n_rows & kCcNoSpan) == 0;
+  n_rows &= ~kCcNoSpan;
   PktCtx c;
   const KeyRow* row;
   constexpr uint32_t kBudget = IMG - kScratchBytes;  // packet images (9728 B at 10 KiB)
@@ -1078,7 +1083,15 @@ __device__ __forceinline__ void chacha_tile(uint32_t tb, uint32_t tid, const Key
   if (total * 16u <= kBudget) {
     pl.slot = incl - nch + (uint32_t)p * pad;
     pool.on = true;
-    DmaStager stg{wsm, arena, arena_len, lane, j, pl};
+    // Span tile (mq_tile.h DmaStager): eight active packets of whole chunks (offset and length
+    // multiples of 16) packed back to back in descriptor order, no gaps between the images — packet
+    // p then lies 16 * slot_p bytes after packet 0, which is the one test that covers all seven
+    // neighbours — so the tile is one linear run in the arena and the same run in LDS. Config B:
+    // 1200 = 75 x 16, an odd chunk count, so no gaps. Staged and, when every packet is still
+    // active at the end, stored as one copy; the layout is the per-packet one byte for byte.
+    const bool in_span = c.act && (((uint32_t)off | pl.len) & 15u) == 0 && off == lane_u64(off, 0) + 16u * pl.slot;
+    const bool span = span_ok && pad == 0 && !wave_any(!in_span);
+    DmaStager stg{wsm, arena, arena_len, lane, j, pl, span ? total : 0u};
     LdsSpace sp{wsm};
     MQ_STAMP(tile_id, 1);
     const uint32_t pkt = pl.slot * 16u + pl.head();
@@ -1086,7 +1099,9 @@ __device__ __forceinline__ void chacha_tile(uint32_t tb, uint32_t tid, const Key
     else ChaChaPolicy::template seal<SINGLE, LdsSpace, DmaStager, IMG, W>(sp, pkt, c, row, j, stg, pool);
     MQ_STAMP(tile_id, 6);
     wave_sync();
-    stage_out(wsm, arena, lane, c.act, pl);
+    // a packet that failed to open is never stored: such a tile goes back packet by packet
+    if (span && !wave_any(!c.act)) stage_out_span(wsm, arena, lane, total, lane_u64(pl.off, 0));
+    else stage_out(wsm, arena, lane, c.act, pl);
     MQ_STAMP(tile_id, 7);
   } else {
     GlobalSpace sp{arena, arena_len};
@@ -1202,7 +1217,10 @@ __device__ __forceinline__ void chacha_list(const KeyRow* __restrict__ kt, uint3
     // tile rather than held in SGPRs across the loop (spilled 29 VGPRs)
     const KeyRow* ktt = kt;
     if (SINGLE && !OPEN) asm volatile("" : "+s"(ktt));
-    chacha_tile<OPEN, SINGLE>(tb, tid, ktt, n_rows, arena, arena_len, desc, n, index, n_dev, status, pn_out, hpm);
+    // no span tiles here: the receive passes' lists are sorted by length class, so their tiles are
+    // rarely back to back, and the second copy loop cost these kernels 4-12 more spilled bytes per lane
+    chacha_tile<OPEN, SINGLE, false, kLdsBytes, W, false>(tb, tid, ktt, n_rows, arena, arena_len, desc, n, index, n_dev,
+                                                          status, pn_out, hpm);
     __syncthreads();  // every wave is done with the tile and its scratch
     if (threadIdx.x == 0) *next_slot = sched ? gridDim.x + pend : tb + gridDim.x;
     __syncthreads();
@@ -1536,26 +1554,29 @@ hipError_t mq_launch_chacha(bool open, const KeyRow* kt, uint32_t n_rows, uint8_
   // single_row >= 0: every packet of the list is on that row (the single-key kernels)
   const bool one = index && single_row >= 0 && (uint64_t)single_row < n_rows;
   const KeyRow* kl = one ? kt + single_row : kt;
+  // MQ_CC_SPAN=0 (diagnostic, mq_opts.h: tests run both copies on one batch): no span tiles in the
+  // octet-tile kernels (chacha_tile reads the bit off n_rows)
+  const uint32_t nr = mq::opt(mq::Opt::CcSpan) == 0 ? n_rows | kCcNoSpan : n_rows;
   if (index && persistent) {
     const uint32_t per = (uint32_t)(cus > 0 ? cus : 256) * 4u, grid = blocks < per ? blocks : per;
     if (open)
       hipLaunchKernelGGL(one ? mq_chacha_open_list1_kernel : mq_chacha_open_list_kernel, dim3(grid),
-                         dim3(kWave * kCcWaves), kLdsBytes * kCcWaves, s, kl, n_rows, arena, arena_len, desc, n, index,
+                         dim3(kWave * kCcWaves), kLdsBytes * kCcWaves, s, kl, nr, arena, arena_len, desc, n, index,
                          n_dev, status, pn_out, hpm, sched, reg);
     else
       hipLaunchKernelGGL(one ? mq_chacha_seal_list1_kernel : mq_chacha_seal_list_kernel, dim3(grid),
-                         dim3(kWave * kCcWaves), kLdsBytes * kCcWaves, s, kl, n_rows, arena, arena_len, desc, n, index,
+                         dim3(kWave * kCcWaves), kLdsBytes * kCcWaves, s, kl, nr, arena, arena_len, desc, n, index,
                          n_dev, status, sched, reg);
     return hipGetLastError();
   }
   if (index) {  // one-shot grid over the list capacity (every region's tiles fit: a tile holds >= 8 entries)
     if (open)
       hipLaunchKernelGGL(one ? mq_chacha_open_lgrid1_kernel : mq_chacha_open_lgrid_kernel, dim3(blocks),
-                         dim3(kWave * kCcWaves), kLdsBytes * kCcWaves, s, kl, n_rows, arena, arena_len, desc, n, index,
+                         dim3(kWave * kCcWaves), kLdsBytes * kCcWaves, s, kl, nr, arena, arena_len, desc, n, index,
                          reg, status, pn_out, hpm);
     else
       hipLaunchKernelGGL(one ? mq_chacha_seal_lgrid1_kernel : mq_chacha_seal_lgrid_kernel, dim3(blocks),
-                         dim3(kWave * kCcWaves), kLdsBytes * kCcWaves, s, kl, n_rows, arena, arena_len, desc, n, index,
+                         dim3(kWave * kCcWaves), kLdsBytes * kCcWaves, s, kl, nr, arena, arena_len, desc, n, index,
                          reg, status);
     return hipGetLastError();
   }
@@ -1588,23 +1609,23 @@ hipError_t mq_launch_chacha(bool open, const KeyRow* kt, uint32_t n_rows, uint8_
       if (open)
         hipLaunchKernelGGL(img == 2 ? (o1 ? mq_chacha_open_longer1_kernel : mq_chacha_open_longer_kernel)
                                     : (o1 ? mq_chacha_open_long1_kernel : mq_chacha_open_long_kernel),
-                           dim3(blocks), dim3(kWave * kCcWaves), lds, s, kt, n_rows, arena, arena_len, desc, n, status,
+                           dim3(blocks), dim3(kWave * kCcWaves), lds, s, kt, nr, arena, arena_len, desc, n, status,
                            pn_out, hpm);
       else
         hipLaunchKernelGGL(img == 2 ? (o1 ? mq_chacha_seal_longer1_kernel : mq_chacha_seal_longer_kernel)
                                     : (o1 ? mq_chacha_seal_long1_kernel : mq_chacha_seal_long_kernel),
-                           dim3(blocks), dim3(kWave * kCcWaves), lds, s, kt, n_rows, arena, arena_len, desc, n, status);
+                           dim3(blocks), dim3(kWave * kCcWaves), lds, s, kt, nr, arena, arena_len, desc, n, status);
       return hipGetLastError();
     }
   }
   if (open)
     hipLaunchKernelGGL(n_rows == 1 || one ? mq_chacha_open1_kernel : mq_chacha_open_kernel, dim3(blocks),
-                       dim3(kWave * kCcWaves), kLdsBytes * kCcWaves, s, kl, n_rows, arena, arena_len, desc, n, index,
+                       dim3(kWave * kCcWaves), kLdsBytes * kCcWaves, s, kl, nr, arena, arena_len, desc, n, index,
                        n_dev, status, pn_out, hpm);
   if (open) return hipGetLastError();
   // seal: header protection runs inside the tile kernel (the pool's HP blocks, cc_pool_run)
   hipLaunchKernelGGL(n_rows == 1 || one ? mq_chacha_seal1_kernel : mq_chacha_seal_kernel, dim3(blocks),
-                     dim3(kWave * kCcWaves), kLdsBytes * kCcWaves, s, kl, n_rows, arena, arena_len, desc, n, index,
+                     dim3(kWave * kCcWaves), kLdsBytes * kCcWaves, s, kl, nr, arena, arena_len, desc, n, index,
                      n_dev, status);
   return hipGetLastError();
 }

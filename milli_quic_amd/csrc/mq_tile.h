@@ -7,6 +7,8 @@
 // (an octet prefix sum of the chunk counts). Staging moves one packet per LDS-DMA instruction
 // group (SGPR base address, lane = chunk), write-back likewise with plain 16-B stores; only the
 // partial first/last chunks of unaligned packets go byte-wise, in one 16-lane pass per tile.
+// A ChaCha20 tile of 16-B-aligned packets packed back to back is one run of chunks in the arena
+// and in LDS alike, and is copied both ways as that one run ("span", DmaStager / stage_out_span).
 // Tiles whose images exceed the LDS budget run the same policy code on HBM directly ("direct").
 #pragma once
 #include "mq_device.h"
@@ -119,12 +121,19 @@ __device__ __forceinline__ uint64_t lane_u64(uint64_t x, int l) {
 // the packet's (SGPR) base + 16 * lane, so every instruction is one contiguous 1-KiB read
 // (tools/ubench/ubench3.hip: 5.5 TB/s). A chunk that would read past the arena end is loaded
 // byte-wise instead. issue() returns immediately; complete() waits.
+//
+// Span tiles (span_chunks != 0, wave-uniform; chacha_tile): the tile's images are one run of
+// span_chunks 16-B chunks in the arena, starting at packet 0's offset, and the same run in LDS from
+// chunk 0 — 16-B-aligned packets packed back to back (a send buffer of equal padded packets).
+// One instruction per 64 chunks of the tile then, not per packet (1200-B packets: 10, not 16); no
+// packet reaches past the arena end (validation), and no chunk is partial, so there is no tail.
 struct DmaStager {
   uint8_t* smem;
   const uint8_t* arena;
   uint64_t arena_len;
   int lane, j;
   Placement pl;
+  uint32_t span_chunks = 0;
 
   __device__ __forceinline__ bool tail_fix() const {  // last chunk reaches past the arena end
     return pl.len && pl.base() + 16ull * pl.nch() > arena_len;
@@ -133,6 +142,14 @@ struct DmaStager {
 #if MQ_PROF_SKIP & 8
     return;
 #endif
+    if (span_chunks) {
+      const uint8_t* src = arena + lane_u64(pl.off, 0) + 16u * (uint32_t)lane;
+      for (uint32_t k = 0; k < span_chunks; k += kWave)
+        if (k + lane < span_chunks)
+          __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src + 16u * k),
+                                           (__attribute__((address_space(3))) void*)(smem + 16u * k), 16, 0, 0);
+      return;
+    }
     const uint32_t ndma = pl.nch() - (tail_fix() ? 1u : 0u);
 #pragma unroll
     for (int q = 0; q < kPktsPerTile; ++q) {
@@ -148,6 +165,7 @@ struct DmaStager {
   }
   __device__ __forceinline__ void complete() {
     wave_sync();  // workgroup-scope fence: s_waitcnt vmcnt(0) covers the LDS-DMA writes
+    if (span_chunks) return;  // wave-uniform
     if (j == 0 && tail_fix())
       *(uint4*)(smem + 16u * (pl.slot + pl.nch() - 1)) =
           load_chunk_guarded(arena, pl.base() + 16ull * (pl.nch() - 1), arena_len);
@@ -203,6 +221,41 @@ __device__ __forceinline__ void stage_out(const uint8_t* smem, uint8_t* arena, i
 #pragma unroll
       for (uint32_t b = 0; b < 16; ++b)
         if (b >= lo && b < hi) dst[b] = (uint8_t)(w[b >> 2] >> (8 * (b & 3)));
+    }
+  }
+}
+
+// LDS -> HBM of a span tile (DmaStager) all of whose packets are written: one linear copy of
+// `chunks` 16-B chunks from LDS chunk 0 to arena + off0 (wave-uniform). The LDS reads go out in
+// groups of kSpanGroup before the first one is waited for, so 600 chunks take two LDS round trips.
+// A lane past the end reads the last chunk again (no predicated read) and stores nothing.
+constexpr int kSpanGroup = 5;
+__device__ __forceinline__ void stage_out_span(const uint8_t* smem, uint8_t* arena, int lane, uint32_t chunks,
+                                               uint64_t off0) {
+#if MQ_PROF_SKIP & 4
+  return;
+#endif
+  uint8_t* dst = arena + off0;  // wave-uniform base, 32-bit lane offsets (the span is under 20 KiB)
+  for (uint32_t k = 0; k < chunks; k += kSpanGroup * kWave) {
+    uint4 v[kSpanGroup];
+#pragma unroll
+    for (int g = 0; g < kSpanGroup; ++g) {
+      const uint32_t c = k + (uint32_t)(g * kWave + lane);
+      v[g] = *(const uint4*)(smem + 16u * (c < chunks ? c : chunks - 1u));
+    }
+    // every read of the group is issued before the first store: without this the compiler sinks
+    // each read into its store's predicated block, one LDS round trip per store again
+#pragma unroll
+    for (int g = 0; g < kSpanGroup; ++g) asm volatile("" : "+v"(v[g].x), "+v"(v[g].y), "+v"(v[g].z), "+v"(v[g].w));
+    if (k + kSpanGroup * kWave <= chunks) {  // wave-uniform: a whole group, nothing predicated
+#pragma unroll
+      for (int g = 0; g < kSpanGroup; ++g) *(uint4*)(dst + 16u * (k + (uint32_t)(g * kWave + lane))) = v[g];
+    } else {
+#pragma unroll
+      for (int g = 0; g < kSpanGroup; ++g) {
+        const uint32_t c = k + (uint32_t)(g * kWave + lane);
+        if (c < chunks) *(uint4*)(dst + 16u * c) = v[g];
+      }
     }
   }
 }
