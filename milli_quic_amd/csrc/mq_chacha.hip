@@ -30,60 +30,84 @@ constexpr uint32_t kKsStride = 68;
 constexpr uint32_t kKsStride = 64;
 #endif
 
-// Interleaved Poly1305 of the AEAD MAC input for the octet's packet (RFC 8439 §2.8: AAD||pad16||
-// CT||pad16||LE64(len AAD)||LE64(len CT)): lane j takes MAC blocks 8k + j, Horner with r^8, one
-// final multiply by r^(8-j), then the octet sum. Every lane of the octet returns the same tag.
-template <class S>
-__device__ __forceinline__ void poly_tag(const S& sp, typename S::off_t pkt, typename S::off_t pay,
-                                         uint32_t aad_len, uint32_t ct_len,
-                                         const uint32_t* otk_lds, int j, bool act,
-                                         uint32_t (&tag)[4]) {
+// The Poly1305 one-time key r || s (words 0..7 of keystream block 0) as poly_tag takes it. Octet
+// tiles: in the packet's 32-B LDS scratch, written by octet lane 0; s is read only once the Horner
+// loop is done. Narrow tiles: in registers, already broadcast over the lane group.
+struct OtkLds {
+  const uint32_t* p;
+  __device__ __forceinline__ void r(uint32_t (&w)[4]) const { u4w(*(const uint4*)p, w); }
+  __device__ __forceinline__ void s(uint32_t (&w)[4]) const { u4w(*(const uint4*)(p + 4), w); }
+};
+struct OtkRegs {
+  uint32_t rk[4], sk[4];
+  __device__ __forceinline__ void r(uint32_t (&w)[4]) const {
+#pragma unroll
+    for (int k = 0; k < 4; ++k) w[k] = rk[k];
+  }
+  __device__ __forceinline__ void s(uint32_t (&w)[4]) const {
+#pragma unroll
+    for (int k = 0; k < 4; ++k) w[k] = sk[k];
+  }
+};
+
+// Interleaved Poly1305 of the AEAD MAC input for the lane group's packet (RFC 8439 §2.8: AAD||pad16||
+// CT||pad16||LE64(len AAD)||LE64(len CT)), G lanes per packet (8: an octet tile, 1 / 2 / 4: narrow
+// tiles): group lane j takes MAC blocks G k + j - z, Horner with r^G, one final multiply by
+// r^(G-j), then the group sum. Every lane of the group returns the same tag.
+template <int G, class S, class K>
+__device__ __forceinline__ void poly_tag(const S& sp, typename S::off_t pkt, typename S::off_t pay, uint32_t aad_len,
+                                         uint32_t ct_len, const K& otk, int j, bool act, uint32_t (&tag)[4]) {
+  typedef Grp<G> Gp;
+  uint32_t rk[4], s[4];
 #if MQ_PROF_SKIP & 2
-  for (int w = 0; w < 4; ++w) tag[w] = otk_lds[4 + w] ^ aad_len ^ ct_len;
+  otk.s(s);
+  for (int w = 0; w < 4; ++w) tag[w] = s[w] ^ aad_len ^ ct_len;
   return;
 #endif
-  const uint4 rk = *(const uint4*)otk_lds;  // one-time key r || s, written by octet lane 0
-  const P26 r = p26_from_words(rk.x & 0x0fffffffu, rk.y & 0x0ffffffcu, rk.z & 0x0ffffffcu,
-                               rk.w & 0x0ffffffcu, 0);
-  // powers by an octet prefix: v = r^(j+1) after three multiplies (r^2, then x r^2 on lanes with
-  // bit 1 of j, then x r^4 — taken from octet lane 3 — on lanes with bit 2); r^8 is octet lane 7's
-  // v, and the final multiplier r^(8-j) is lane 7-j's v (DPP row_half_mirror)
-  P26 v = r, t = r;
-  p26_mul(t, p26_mult(r));  // r^2
+  otk.r(rk);
+  const P26 r = p26_from_words(rk[0] & 0x0fffffffu, rk[1] & 0x0ffffffcu, rk[2] & 0x0ffffffcu, rk[3] & 0x0ffffffcu, 0);
+  // powers by a group prefix: v = r^(j+1) after up to three multiplies (r^2, then x r^2 on lanes
+  // with bit 1 of j, then x r^4 — taken from octet lane 3 — on lanes with bit 2); r^G is the last
+  // group lane's v, and the final multiplier r^(G-j) is lane G-1-j's v (the group mirror)
+  P26 v = r, rG = r, rj = r;
+  if (G >= 2) {
+    P26 t = r;
+    p26_mul(t, p26_mult(r));  // r^2
 #pragma unroll
-  for (int l = 0; l < 5; ++l) v.l[l] = (j & 1) ? t.l[l] : v.l[l];
-  {
-    P26 u = v;
-    p26_mul(u, p26_mult(t));
+    for (int l = 0; l < 5; ++l) v.l[l] = (j & 1) ? t.l[l] : v.l[l];
+    if (G >= 4) {
+      P26 u = v;
+      p26_mul(u, p26_mult(t));
 #pragma unroll
-    for (int l = 0; l < 5; ++l) v.l[l] = (j & 2) ? u.l[l] : v.l[l];
+      for (int l = 0; l < 5; ++l) v.l[l] = (j & 2) ? u.l[l] : v.l[l];
+    }
+    if (G == 8) {
+      P26 r4, u = v;
+#pragma unroll
+      for (int l = 0; l < 5; ++l) r4.l[l] = oct_lane3(v.l[l]);
+      p26_mul(u, p26_mult(r4));
+#pragma unroll
+      for (int l = 0; l < 5; ++l) v.l[l] = (j & 4) ? u.l[l] : v.l[l];
+    }
+#pragma unroll
+    for (int l = 0; l < 5; ++l) {
+      rG.l[l] = Gp::last(v.l[l]);
+      rj.l[l] = Gp::mirror(v.l[l]);
+    }
   }
-  {
-    P26 r4, u = v;
-#pragma unroll
-    for (int l = 0; l < 5; ++l) r4.l[l] = oct_lane3(v.l[l]);
-    p26_mul(u, p26_mult(r4));
-#pragma unroll
-    for (int l = 0; l < 5; ++l) v.l[l] = (j & 4) ? u.l[l] : v.l[l];
-  }
-  P26 r8, rj;
-#pragma unroll
-  for (int l = 0; l < 5; ++l) {
-    r8.l[l] = oct_lane7(v.l[l]);
-    rj.l[l] = half_mirror(v.l[l]);
-  }
-  const P26m m8 = p26_mult(r8), mlast = p26_mult(rj);
+  const P26m mG = p26_mult(rG), mlast = p26_mult(rj);
 
   const uint32_t A = (aad_len + 15) >> 4, T = (ct_len + 15) >> 4, nb = A + T + 1;
-  const uint32_t K = (nb + kLanesPerPkt - 1) / kLanesPerPkt;
-  const uint32_t Kmax = wave_max_u32(act ? K : 0u);
+  const uint32_t K_ = (nb + G - 1) / G;
+  // per-packet values are group-uniform: the group reductions
+  const uint32_t Kmax = Gp::wave_max(act ? K_ : 0u);
   // prepend zero blocks (no 2^128 bit) so every packet of the wave runs exactly Kmax steps
-  const int z = (int)(kLanesPerPkt * Kmax) - (int)nb;
+  const int z = (int)(G * Kmax) - (int)nb;
   P26 acc;
 #pragma unroll
   for (int l = 0; l < 5; ++l) acc.l[l] = 0;
 
-  // MAC block i = 8k + j - z of this lane: where it lives, how many of its bytes are real
+  // MAC block i = G k + j - z of this lane: where it lives, how many of its bytes are real
   struct Blk { typename S::off_t src; int rem; bool pre, lens; };
   auto where = [&](int i) {
     Blk b;
@@ -111,19 +135,19 @@ __device__ __forceinline__ void poly_tag(const S& sp, typename S::off_t pkt, typ
     Blk b = where(i);
     uint32_t m[4];
     load_words<4>(sp, b.src, m);
-    // steady state: every active lane moves from one whole ciphertext block to the next one 8
-    // blocks on (src + 128, payload alignment fixed), so the address and realignment selector
+    // steady state: every active lane moves from one whole ciphertext block to the next one G
+    // blocks on (src + 16 G, payload alignment fixed), so the address and realignment selector
     // need no per-step recomputation
     const uint32_t sel_pay = sel_load((uint32_t)(pay & 3));
     const int ct_full_end = (int)A + (int)(ct_len >> 4);  // first index past the whole CT blocks
     // lean steps k in [k_lo, k_hi): every active lane absorbs a whole ciphertext block and loads
-    // the next whole one (8j + ... - z in [A, ct_full_end - 8)), so no masks, 2^128 bit selects
+    // the next whole one (G k + j - z in [A, ct_full_end - G)), so no masks, 2^128 bit selects
     // or address recomputation
     const int zA = (int)A + z;
-    const uint32_t k_lo = act ? (uint32_t)((zA + kLanesPerPkt - 1) / kLanesPerPkt) : 0u;
-    const int hi = ct_full_end + z - 2 * kLanesPerPkt + 1;  // lean iff 8k + 15 - z < ct_full_end
-    const uint32_t k_hi = !act ? 0xFFFFFFFFu : (hi <= 0 ? 0u : (uint32_t)((hi + kLanesPerPkt - 1) / kLanesPerPkt));
-    const uint32_t klo = wave_max_u32(k_lo), khi = min(~wave_max_u32(~k_hi), Kmax - 1);
+    const uint32_t k_lo = act ? (uint32_t)((zA + G - 1) / G) : 0u;
+    const int hi = ct_full_end + z - 2 * G + 1;  // lean iff G k + 2G - 1 - z < ct_full_end
+    const uint32_t k_hi = !act ? 0xFFFFFFFFu : (hi <= 0 ? 0u : (uint32_t)((hi + G - 1) / G));
+    const uint32_t klo = Gp::wave_max(k_lo), khi = min(Gp::wave_min(k_hi), Kmax - 1);
     for (uint32_t k = 0; k + 1 < Kmax; ++k) {
       if (k == klo && k < khi) {  // wave-uniform: the lean stretch, steps klo .. khi - 1
         // only the block address advances; i, src and rem catch up once at the end
@@ -134,36 +158,35 @@ __device__ __forceinline__ void poly_tag(const S& sp, typename S::off_t pkt, typ
           const P26 x = p26_from_words(m[0], m[1], m[2], m[3], 1u);
 #pragma unroll
           for (int l = 0; l < 5; ++l) acc.l[l] += x.l[l];
-          a += 128;
+          a += 16 * G;
           load_words_sel<4>(sp, a, sel, m);
-          p26_mul(acc, m8);
+          p26_mul(acc, mG);
         }
         const uint32_t nl = khi - klo;
-        i += (int)(kLanesPerPkt * nl);
-        b.src += 128 * nl;
-        b.rem -= (int)(128 * nl);
+        i += (int)(G * nl);
+        b.src += 16 * G * nl;
+        b.rem -= (int)(16 * G * nl);
         if (k + 1 >= Kmax) break;
       }
       absorb(b, m);
-      const bool steady = !act || (i >= (int)A && i + kLanesPerPkt < ct_full_end);
-      i += kLanesPerPkt;
+      const bool steady = !act || (i >= (int)A && i + G < ct_full_end);
+      i += G;
       if (!wave_any(!steady)) {
-        b.src += 128;
-        b.rem -= 128;
+        b.src += 16 * G;
+        b.rem -= 16 * G;
         load_words_sel<4>(sp, b.src & ~(typename S::off_t)3, sel_pay, m);
       } else {
         b = where(i);
         load_words<4>(sp, b.src, m);  // next block's LDS reads overlap this multiply
       }
-      p26_mul(acc, m8);
+      p26_mul(acc, mG);
     }
     absorb(b, m);
     p26_mul(acc, mlast);
   }
 #pragma unroll
-  for (int l = 0; l < 5; ++l) acc.l[l] = oct_sum(acc.l[l]);
-  const uint4 sk = *(const uint4*)(otk_lds + 4);
-  const uint32_t s[4] = {sk.x, sk.y, sk.z, sk.w};
+  for (int l = 0; l < 5; ++l) acc.l[l] = Gp::sum(acc.l[l]);
+  otk.s(s);
   p26_finish(acc, s, tag);
 }
 
@@ -269,19 +292,21 @@ __device__ __forceinline__ void cc_pool_run(const CcPool& pool, uint32_t tid = t
   }
 }
 
-// RFC 9001 §5.4.1: XOR the mask into the first byte (low 4 / 5 bits) and the PN bytes of a sealed
-// packet whose MAC has been computed (octet lane 0)
-template <class S>
-__device__ __forceinline__ void apply_hp(const S& sp, typename S::off_t pkt, const mq_pkt_desc& d, uint32_t m0,
-                                         uint32_t m1) {
-  sp.st8(pkt, (uint8_t)(sp.ld8(pkt) ^ ((uint8_t)m0 & ((d.flags & MQ_PKT_LONG_HEADER) ? 0x0f : 0x1f))));
-  const uint32_t mk = (m0 >> 8) | (m1 << 24);
-  for (uint32_t b = 0; b < d.pn_len; ++b)
-    sp.st8(pkt + d.pn_offset + b, (uint8_t)(sp.ld8(pkt + d.pn_offset + b) ^ (uint8_t)(mk >> (8 * b))));
-}
-
+// The tile code of both layouts: octet tiles (8 lanes per packet, the keystream pool; chacha_tile,
+// chacha_protect_tile) and narrow tiles (G = 1, 2, 4 or 8 lanes per packet, no pool; narrow_tile).
 struct ChaChaPolicy {
   static constexpr uint32_t kSuite = MQ_SUITE_CHACHA20;
+
+  // RFC 9001 §5.4.1: XOR the mask into the first byte (low 4 / 5 bits) and the PN bytes of a sealed
+  // packet whose MAC has been computed (one lane of the packet's group)
+  template <class S>
+  static __device__ __forceinline__ void apply_hp(const S& sp, typename S::off_t pkt, const mq_pkt_desc& d,
+                                                  uint32_t m0, uint32_t m1) {
+    sp.st8(pkt, (uint8_t)(sp.ld8(pkt) ^ ((uint8_t)m0 & ((d.flags & MQ_PKT_LONG_HEADER) ? 0x0f : 0x1f))));
+    const uint32_t mk = (m0 >> 8) | (m1 << 24);
+    for (uint32_t b = 0; b < d.pn_len; ++b)
+      sp.st8(pkt + d.pn_offset + b, (uint8_t)(sp.ld8(pkt + d.pn_offset + b) ^ (uint8_t)(mk >> (8 * b))));
+  }
 
   // raw LDS/HBM dwords under keystream block `ctr` (>= 1): payload [64(ctr-1), min(64 ctr, P))
   template <class S>
@@ -319,26 +344,78 @@ struct ChaChaPolicy {
     hp_mask_words(smp, row, m0, m1);
   }
 
+  // What both send composites start from: the packet's content key and nonce, and its geometry
+  template <class S>
+  struct SealPkt {
+    uint32_t key[8], n0, n1, n2;
+    uint32_t aad_len, P;      // header (the AAD) and payload bytes
+    uint32_t nblk;            // ChaCha20 blocks: 0 = Poly1305 key, 1.. = keystream
+    typename S::off_t pay;    // the payload
+    bool hp;                  // header protection applies (records and plain AEAD rows have none)
+
+    // SCALAR: wave-uniform key material goes to SGPRs. Else it is pinned, and the nonce always is:
+    // their loads retire before the caller issues the stager's LDS-DMA (else the first wait covers
+    // the DMA too).
+    template <bool SCALAR>
+    __device__ __forceinline__ void load(typename S::off_t pkt, const PktCtx& c, const KeyRow* row) {
+      const mq_pkt_desc& d = c.d;
+      load_key8(row->key, key);
+      aad_len = c.act ? (uint32_t)d.pn_offset + d.pn_len : 0u;
+      P = c.act ? d.len - aad_len - 16 : 0u;
+      pay = pkt + aad_len;
+      // DirectionalKeys::nonce (src/crypto/mod.rs:66-74): iv ^ (0^32 || BE64(pn))
+      n0 = row->iv[0];
+      n1 = row->iv[1] ^ bswap32((uint32_t)(c.pn >> 32));
+      n2 = row->iv[2] ^ bswap32((uint32_t)c.pn);
+#pragma unroll
+      for (int i = 0; i < 8; ++i) {
+        if (SCALAR) key[i] = __builtin_amdgcn_readfirstlane(key[i]);
+        else pin(key[i]);
+      }
+      pin(n0); pin(n1); pin(n2);
+      nblk = 1 + (P + 63) / 64;
+      hp = c.act && !(d.flags & MQ_PKT_NO_HP);
+    }
+  };
+
+  // What both end with: the tag behind the payload, then header protection (transmit.rs:713-738)
+  // now that the MAC has read the unprotected header. have: the packet's mask (m0, m1) was made in
+  // a keystream slot and is on group lane jh; the other packets' masks this wave computes late, on
+  // every lane of the group.
+  template <class S>
+  static __device__ __forceinline__ void seal_finish(const S& sp, typename S::off_t pkt, const PktCtx& c,
+                                                     const KeyRow* row, int j, const SealPkt<S>& k,
+                                                     const uint32_t (&tag)[4], bool have, int jh, uint32_t m0,
+                                                     uint32_t m1) {
+    if (c.act && j == 0) store_words<4>(sp, k.pay + k.P, tag);
+    const bool late = k.hp && !have;
+    if (wave_any(late)) {
+      wave_sync();  // ciphertext and tags are in place
+      uint32_t a0, a1;
+      hp_mask(sp, pkt + c.d.pn_offset + 4, row, a0, a1);
+      if (late) {
+        m0 = a0;
+        m1 = a1;
+      }
+    }
+    wave_sync();
+    if (k.hp && j == jh) apply_hp(sp, pkt, c.d, m0, m1);
+    wave_sync();
+  }
+
   // send composite (transmit.rs:625-755): keystream block ctr of the packet runs on lane ctr % 8 in
   // iteration ctr / 8 (ctr 0 = the Poly1305 key); with the pool, blocks >= 16 and the
   // header-protection block (its sample is ciphertext of block 1) run in the workgroup's pool
   // before the MACs, and the mask is applied once the MAC has read the unprotected header.
-  template <bool SINGLE, class S, class G, uint32_t IMG = kLdsBytes, uint32_t W = kCcWaves>
+  template <bool SINGLE, uint32_t IMG = kLdsBytes, uint32_t W = kCcWaves, class S, class St>
   static __device__ __forceinline__ void seal(const S& sp, typename S::off_t pkt, PktCtx& c, const KeyRow* row, int j,
-                                              G& stg, const CcPool& pool) {
+                                              St& stg, const CcPool& pool) {
     const mq_pkt_desc& d = c.d;
-    uint32_t key[8];
-    load_key8(row->key, key);
-    const uint32_t aad_len = c.act ? (uint32_t)d.pn_offset + d.pn_len : 0u;
-    const uint32_t P = c.act ? d.len - aad_len - 16 : 0u;
-    const typename S::off_t pay = pkt + aad_len;
-    // DirectionalKeys::nonce (src/crypto/mod.rs:66-74): iv ^ (0^32 || BE64(pn))
-    uint32_t n0 = row->iv[0], n1 = row->iv[1] ^ bswap32((uint32_t)(c.pn >> 32)), n2 = row->iv[2] ^ bswap32((uint32_t)c.pn);
-#pragma unroll
-    for (int k = 0; k < 8; ++k) pin(key[k]);
-    pin(n0); pin(n1); pin(n2);
+    SealPkt<S> k;
+    k.template load<false>(pkt, c, row);
+    const uint32_t P = k.P, nblk = k.nblk;
+    const typename S::off_t pay = k.pay;
     stg.issue();  // packet bytes stream into LDS while the first keystream block is computed
-    const uint32_t nblk = 1 + (P + 63) / 64;  // block 0 = Poly1305 key, 1.. = keystream
     const uint32_t kst = pool.on ? min(nblk, kCcPoolSlot) : nblk;  // blocks of this wave's own slots
     const uint32_t Imax = wave_max_u32(c.act ? (kst + kLanesPerPkt - 1) / kLanesPerPkt : 0u);
     for (uint32_t it = 0; it < Imax; ++it) {
@@ -347,7 +424,7 @@ struct ChaChaPolicy {
       uint32_t w[17];
       if (it > 0) load_block(sp, pay, a ? ctr : 0u, w);  // LDS reads in flight during the block function
       uint32_t ks[16];
-      chacha20_block(key, ctr, n0, n1, n2, ks);
+      chacha20_block(k.key, ctr, k.n0, k.n1, k.n2, ks);
       if (it == 0) {
         stg.complete();
         MQ_STAMP(c.tile, 2);
@@ -366,10 +443,9 @@ struct ChaChaPolicy {
       wave_sync();
     }
     if (Imax == 0) stg.complete();
-    const bool hp = c.act && !(d.flags & MQ_PKT_NO_HP);  // records and plain AEAD rows have none
     // the pool takes the HP block when the sample (payload bytes [4 - pn_len, 20 - pn_len)) is all
     // ciphertext; for tiny payloads it reaches into the tag, which only the MAC below produces
-    const bool hp_pool = pool.on && hp && P + d.pn_len >= 20u;
+    const bool hp_pool = pool.on && k.hp && P + d.pn_len >= 20u;
     if (j == 0) {  // pool record: keystream blocks >= 16 and the HP block
       const uint32_t np = pool.on && c.act && nblk > kCcPoolSlot ? nblk - kCcPoolSlot : 0u;
       const uint32_t hpn = hp_pool ? (uint32_t)d.pn_len : 0u;  // 1..4 (validated)
@@ -377,7 +453,7 @@ struct ChaChaPolicy {
       if (np || hpn) {
         pool.rec[1] = (pool.base + (uint32_t)pay) | P << 17;
         pool.rec[3] = d.key_id;
-        pool.rec[4] = n0; pool.rec[5] = n1; pool.rec[6] = n2;
+        pool.rec[4] = k.n0; pool.rec[5] = k.n1; pool.rec[6] = k.n2;
       }
     }
     __syncthreads();  // every wave's records
@@ -385,33 +461,102 @@ struct ChaChaPolicy {
     __syncthreads();  // every pooled block (and mask) is in place before any MAC reads it
     MQ_STAMP(c.tile, 3);
     uint32_t tag[4];
-    poly_tag(sp, pkt, pay, aad_len, P, c.otk, j, c.act, tag);
-    if (c.act && j == 0) store_words<4>(sp, pay + P, tag);
-    // header protection (transmit.rs:713-738), now that the MAC has read the unprotected header
+    poly_tag<kLanesPerPkt>(sp, pkt, pay, k.aad_len, P, OtkLds{c.otk}, j, c.act, tag);
+    // the pooled mask waits in the record; without one (direct path, or a sample that reaches
+    // into the tag) the wave computes it late; octet lane 0 applies either
     uint32_t m0 = 0, m1 = 0;
     if (hp_pool) {
       m0 = pool.rec[2];
       m1 = pool.rec[7];
     }
-    const bool late = hp && !hp_pool;  // direct path, or a sample that reaches into the tag
-    if (wave_any(late)) {  // this wave computes those masks itself
-      wave_sync();  // ciphertext and tags are in place
-      uint32_t a0, a1;
-      hp_mask(sp, pkt + d.pn_offset + 4, row, a0, a1);
-      if (late) {
-        m0 = a0;
-        m1 = a1;
-      }
-    }
-    if (hp && j == 0) apply_hp(sp, pkt, d, m0, m1);
-    wave_sync();
+    seal_finish(sp, pkt, c, row, j, k, tag, hp_pool, 0, m0, m1);
     MQ_STAMP(c.tile, 4);
   }
 
-  // receive composite (recv.rs:340-421 / 953-1025): HP removal, decode_pn, open.
-  template <bool SINGLE, class S, class G, uint32_t IMG = kLdsBytes, uint32_t W = kCcWaves>
+  // send composite (transmit.rs:625-755) on a narrow tile. Slot order: keystream blocks 1 .. nblk-1
+  // first, the one-time key (block 0) in slot nblk - 1 — made last, so its 8 words are not held
+  // through the loop — then the header-protection block in slot nblk.
+  template <int G, bool SINGLE, class S, class St>
+  static __device__ __forceinline__ void seal_narrow(const S& sp, typename S::off_t pkt, PktCtx& c, const KeyRow* row,
+                                                     int j, St& stg) {
+    const mq_pkt_desc& d = c.d;
+    SealPkt<S> k;
+    k.template load<SINGLE>(pkt, c, row);  // a single-key tile keeps its key in SGPRs
+    const uint32_t P = k.P, nblk = k.nblk;
+    const typename S::off_t pay = k.pay;
+    stg.issue();
+    // the header-protection block in slot nblk: its sample (payload [4 - pn_len, 20 - pn_len)) is
+    // ciphertext of keystream block 1 (slot 0, iteration 0), so slot nblk must fall in a later
+    // iteration (nblk >= G), and must not reach into the tag (only the MAC produces it)
+    const bool hp_in = k.hp && P + d.pn_len >= 20u && nblk >= (uint32_t)G;
+    const uint32_t S_ = nblk + (hp_in ? 1u : 0u);
+    const uint32_t Imax = wave_max_any(c.act ? (S_ + G - 1) / G : 0u);
+    uint32_t otk[8] = {0, 0, 0, 0, 0, 0, 0, 0}, m0 = 0, m1 = 0;
+    for (uint32_t it = 0; it < Imax; ++it) {
+      const uint32_t slot = (uint32_t)j + G * it;
+      const bool is_otk = c.act && slot + 1 == nblk;
+      const uint32_t ctr = is_otk ? 0u : slot + 1;  // keystream block of the slot
+      const bool a = c.act && ctr < nblk;            // a keystream block (or the one-time key)
+      const bool is_hp = hp_in && slot == nblk;
+      uint32_t ks[16];
+      if (wave_any(is_hp)) {  // the HP lanes run the HP key on the sample (ciphertext by now)
+        uint32_t smp[4], kh[8], kk[8];
+        load_words<4>(sp, is_hp ? pay + 4u - d.pn_len : pay, smp);
+        load_key8(row->hp, kh);
+#pragma unroll
+        for (int i = 0; i < 8; ++i) kk[i] = is_hp ? kh[i] : k.key[i];
+        chacha20_block(kk, is_hp ? smp[0] : ctr, is_hp ? smp[1] : k.n0, is_hp ? smp[2] : k.n1, is_hp ? smp[3] : k.n2,
+                       ks);
+      } else {
+        chacha20_block(k.key, ctr, k.n0, k.n1, k.n2, ks);
+      }
+      if (it == 0) {
+        stg.complete();
+        const bool rec = c.act && is_record(d);
+        if (wave_any(rec)) {  // TLS record: header (AAD) and inner content type before any use
+          if (rec && j == 0) write_record_header(sp, pkt, d);
+          wave_sync();
+        }
+      }
+      // the block's raw LDS words after the rounds (not in flight during them: 17 VGPRs fewer)
+      uint32_t w[17];
+      load_block(sp, pay, a && !is_otk ? ctr : 0u, w);
+      if (is_otk) {
+#pragma unroll
+        for (int i = 0; i < 8; ++i) otk[i] = ks[i];
+      } else if (a) {
+        store_block(sp, pay, ctr, P, ks, w);
+      }
+      if (is_hp) {
+        m0 = ks[0];
+        m1 = ks[1];
+      }
+      wave_sync();
+    }
+    if (Imax == 0) stg.complete();
+    // the one-time key from its group lane (nblk - 1) % G to the whole group
+    OtkRegs rs;
+    uint32_t tag[4];
+    const int src = (int)(threadIdx.x & (kWave - 1)) - j + (int)((nblk + G - 1) % G);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      rs.rk[i] = G == 1 ? otk[i] : (uint32_t)__shfl((int)otk[i], src, kWave);
+      rs.sk[i] = G == 1 ? otk[4 + i] : (uint32_t)__shfl((int)otk[4 + i], src, kWave);
+    }
+    poly_tag<G>(sp, pkt, pay, k.aad_len, P, rs, j, c.act, tag);
+    // the mask is on group lane nblk % G when slot nblk made it; tiny payloads and G > nblk: one
+    // more block for the wave
+    seal_finish(sp, pkt, c, row, j, k, tag, hp_in, hp_in ? (int)(nblk % G) : 0, m0, m1);
+  }
+
+  // receive composite (recv.rs:340-421 / 953-1025): HP removal, decode_pn, open — verify, only then
+  // decrypt. G lanes per packet. POOL (the octet tiles of chacha_tile): the one-time key goes
+  // through the packet's LDS scratch and keystream blocks >= 16 to the workgroup's pool, both
+  // barriers included; else (narrow tiles) the key travels by DPP and the wave runs every block.
+  template <int G, bool POOL, bool SINGLE, uint32_t IMG = kLdsBytes, uint32_t W = kCcWaves, class S, class St>
   static __device__ __forceinline__ void open(const S& sp, typename S::off_t pkt, PktCtx& c, const KeyRow* row, int j,
-                              bool direct, G& stg, const CcPool& pool) {
+                                              bool direct, St& stg, const CcPool& pool = CcPool{}) {
+    typedef Grp<G> Gp;
     const mq_pkt_desc& d = c.d;
     stg.issue();
     uint32_t pn_len = d.pn_len, trunc = 0;
@@ -425,10 +570,10 @@ struct ChaChaPolicy {
       if (hp) b0 = header_from_prepass(c, pn_len, trunc);
     } else {
       stg.complete();
-      if (hp) {
+      if (wave_any(hp)) {  // every lane of a group computes its packet's mask (one block for the wave)
         uint32_t m0, m1;
-        hp_mask(sp, pkt + d.pn_offset + 4, row, m0, m1);
-        b0 = header_from_mask(sp, pkt, c, m0, m1, pn_len, trunc);
+        hp_mask(sp, hp ? pkt + d.pn_offset + 4 : pkt, row, m0, m1);
+        if (hp) b0 = header_from_mask(sp, pkt, c, m0, m1, pn_len, trunc);
       }
     }
     uint32_t key[8];
@@ -439,20 +584,29 @@ struct ChaChaPolicy {
     const uint32_t n0 = row->iv[0], n1 = row->iv[1] ^ bswap32((uint32_t)(c.pn >> 32)),
                    n2 = row->iv[2] ^ bswap32((uint32_t)c.pn);
     const uint32_t nblk = 1 + (P + 63) / 64;
-    const uint32_t C = (nblk + kLanesPerPkt - 1) / kLanesPerPkt;
-    const uint32_t Cmax = wave_max_u32(c.act ? C : 0u);
-    // first keystream block of every lane is computed before the MAC (lane 0: one-time key)
+    const uint32_t Cmax = Gp::wave_max(c.act ? (nblk + G - 1) / G : 0u);
+    // first keystream block of every lane is computed before the MAC (group lane 0: one-time key)
     const uint32_t ctr0 = (uint32_t)j;
     uint32_t ks0[16];
     chacha20_block(key, ctr0, n0, n1, n2, ks0);
     if (c.pre_hp) stg.complete();
-    MQ_STAMP(c.tile, 2);
+    if (POOL) MQ_STAMP(c.tile, 2);
     const bool hdr_written = hp && write_unmasked_header(sp, pkt, c, j, b0, pn_len, trunc, orig_b0, orig_pn);
-    MQ_STAMP(c.tile, 3);
-    if (c.act && j == 0) store_otk(c.otk, ks0);
+    if (POOL) MQ_STAMP(c.tile, 3);
+    if (POOL && c.act && j == 0) store_otk(c.otk, ks0);
     wave_sync();
     uint32_t tag[4], got[4];
-    poly_tag(sp, pkt, pay, aad_len, P, c.otk, j, c.act, tag);
+    if (POOL) {
+      poly_tag<G>(sp, pkt, pay, aad_len, P, OtkLds{c.otk}, j, c.act, tag);
+    } else {
+      OtkRegs rs;
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        rs.rk[i] = Gp::bcast0(ks0[i]);
+        rs.sk[i] = Gp::bcast0(ks0[4 + i]);
+      }
+      poly_tag<G>(sp, pkt, pay, aad_len, P, rs, j, c.act, tag);
+    }
     load_words<4>(sp, pay + P, got);
     const uint32_t diff = (tag[0] ^ got[0]) | (tag[1] ^ got[1]) | (tag[2] ^ got[2]) | (tag[3] ^ got[3]);
     if (c.act && diff != 0) {  // Error::Crypto, buffer left as received
@@ -460,15 +614,15 @@ struct ChaChaPolicy {
       c.act = false;
     }
     wave_sync();  // every lane's MAC reads precede any plaintext write
-    MQ_STAMP(c.tile, 4);
+    if (POOL) MQ_STAMP(c.tile, 4);
     if (c.act && ctr0 >= 1 && ctr0 < nblk) {
       uint32_t w[17];
       load_block(sp, pay, ctr0, w);
       store_block(sp, pay, ctr0, P, ks0, w);
     }
-    const uint32_t Cown = pool.on ? min(Cmax, kCcOwnIters) : Cmax;  // later slots: the workgroup's pool
+    const uint32_t Cown = POOL && pool.on ? min(Cmax, kCcOwnIters) : Cmax;  // later slots: the workgroup's pool
     for (uint32_t it = 1; it < Cown; ++it) {
-      const uint32_t ctr = (uint32_t)j + kLanesPerPkt * it;
+      const uint32_t ctr = (uint32_t)j + G * it;
       const bool a = c.act && ctr < nblk;
       uint32_t w[17];
       load_block(sp, pay, a ? ctr : 0u, w);
@@ -476,19 +630,23 @@ struct ChaChaPolicy {
       chacha20_block(key, ctr, n0, n1, n2, ks);
       if (a) store_block(sp, pay, ctr, P, ks, w);
     }
-    if (j == 0) {  // pool record: only verified packets are decrypted (no HP block on open)
-      const uint32_t np = pool.on && c.act && nblk > kCcPoolSlot ? nblk - kCcPoolSlot : 0u;
-      pool.rec[0] = np;
-      if (np) {
-        pool.rec[1] = (pool.base + (uint32_t)pay) | P << 17;
-        pool.rec[3] = d.key_id;
-        pool.rec[4] = n0; pool.rec[5] = n1; pool.rec[6] = n2;
+    if constexpr (POOL) {
+      if (j == 0) {  // pool record: only verified packets are decrypted (no HP block on open)
+        const uint32_t np = pool.on && c.act && nblk > kCcPoolSlot ? nblk - kCcPoolSlot : 0u;
+        pool.rec[0] = np;
+        if (np) {
+          pool.rec[1] = (pool.base + (uint32_t)pay) | P << 17;
+          pool.rec[3] = d.key_id;
+          pool.rec[4] = n0; pool.rec[5] = n1; pool.rec[6] = n2;
+        }
       }
+      __syncthreads();  // every wave's MAC has read its ciphertext
+      cc_pool_run<SINGLE, IMG, W>(pool);
+      __syncthreads();
+      MQ_STAMP(c.tile, 5);
+    } else {
+      wave_sync();
     }
-    __syncthreads();  // every wave's MAC has read its ciphertext
-    cc_pool_run<SINGLE, IMG, W>(pool);
-    __syncthreads();
-    MQ_STAMP(c.tile, 5);
     if (direct && hdr_written && !c.act) {  // direct path writes HBM in place: undo the unmask
       sp.st8(pkt, orig_b0);
       for (uint32_t b = 0; b < pn_len; ++b) sp.st8(pkt + d.pn_offset + b, (uint8_t)(orig_pn >> (8 * b)));
@@ -599,308 +757,6 @@ __device__ __forceinline__ void narrow_stage_out(const uint8_t* smem, uint8_t* a
   }
 }
 
-// Poly1305 tag of a narrow tile's packet (poly_tag with G lanes): lane j takes MAC blocks
-// G k + j - z, Horner with r^G, final multiply by r^(G - j), group sum. r, s: the one-time key.
-template <int G, class S>
-__device__ __forceinline__ void poly_tag_g(const S& sp, typename S::off_t pkt, typename S::off_t pay, uint32_t aad_len,
-                                           uint32_t ct_len, const uint32_t (&rk)[4], const uint32_t (&s)[4], int j,
-                                           bool act, uint32_t (&tag)[4]) {
-#if MQ_PROF_SKIP & 2
-  for (int w = 0; w < 4; ++w) tag[w] = s[w] ^ rk[w] ^ aad_len ^ ct_len;
-  return;
-#endif
-  typedef Grp<G> Gp;
-  const P26 r = p26_from_words(rk[0] & 0x0fffffffu, rk[1] & 0x0ffffffcu, rk[2] & 0x0ffffffcu, rk[3] & 0x0ffffffcu, 0);
-  // powers: v = r^(j + 1) on group lane j; rG = r^G, rj = r^(G - j)
-  P26 v = r, rG = r, rj = r;
-  if (G >= 2) {
-    P26 t = r;
-    p26_mul(t, p26_mult(r));  // r^2
-#pragma unroll
-    for (int l = 0; l < 5; ++l) v.l[l] = (j & 1) ? t.l[l] : v.l[l];
-    if (G >= 4) {
-      P26 u = v;
-      p26_mul(u, p26_mult(t));
-#pragma unroll
-      for (int l = 0; l < 5; ++l) v.l[l] = (j & 2) ? u.l[l] : v.l[l];
-    }
-    if (G == 8) {
-      P26 r4, u = v;
-#pragma unroll
-      for (int l = 0; l < 5; ++l) r4.l[l] = oct_lane3(v.l[l]);
-      p26_mul(u, p26_mult(r4));
-#pragma unroll
-      for (int l = 0; l < 5; ++l) v.l[l] = (j & 4) ? u.l[l] : v.l[l];
-    }
-#pragma unroll
-    for (int l = 0; l < 5; ++l) {
-      rG.l[l] = Gp::last(v.l[l]);
-      rj.l[l] = Gp::mirror(v.l[l]);
-    }
-  }
-  const P26m mG = p26_mult(rG), mlast = p26_mult(rj);
-  const uint32_t A = (aad_len + 15) >> 4, T = (ct_len + 15) >> 4, nb = A + T + 1;
-  const uint32_t K = (nb + G - 1) / G;
-  const uint32_t Kmax = wave_max_any(act ? K : 0u);
-  const int z = (int)(G * Kmax) - (int)nb;  // prepended zero blocks: every packet runs Kmax steps
-  P26 acc;
-#pragma unroll
-  for (int l = 0; l < 5; ++l) acc.l[l] = 0;
-  struct Blk { typename S::off_t src; int rem; bool pre, lens; };
-  auto where = [&](int i) {
-    Blk b;
-    const bool aad = i < (int)A;
-    b.pre = i < 0;
-    b.lens = i == (int)(A + T);
-    b.src = aad ? pkt + 16 * (uint32_t)max(i, 0) : pay + 16 * (uint32_t)(i - (int)A);
-    b.rem = aad ? (int)aad_len - 16 * i : (int)ct_len - 16 * (i - (int)A);
-    if (b.pre || b.lens) b.src = pkt;
-    return b;
-  };
-  auto absorb = [&](const Blk& b, uint32_t (&m)[4]) {
-    if (wave_any(act && (b.pre || b.lens || b.rem < 16))) {
-#pragma unroll
-      for (int w = 0; w < 4; ++w) m[w] &= byte_mask(b.pre ? 0 : b.rem, w);
-      if (b.lens) { m[0] = aad_len; m[1] = 0; m[2] = ct_len; m[3] = 0; }
-    }
-    const P26 x = p26_from_words(m[0], m[1], m[2], m[3], b.pre ? 0u : 1u);
-#pragma unroll
-    for (int l = 0; l < 5; ++l) acc.l[l] += x.l[l];
-  };
-  if (Kmax > 0) {
-    int i = j - z;
-    Blk b = where(i);
-    uint32_t m[4];
-    load_words<4>(sp, b.src, m);
-    const uint32_t sel_pay = sel_load((uint32_t)(pay & 3));
-    const int ct_full_end = (int)A + (int)(ct_len >> 4);
-    const int zA = (int)A + z;
-    const uint32_t k_lo = act ? (uint32_t)((zA + G - 1) / G) : 0u;
-    const int hi = ct_full_end + z - 2 * G + 1;  // lean iff G k + 2G - 1 - z < ct_full_end
-    const uint32_t k_hi = !act ? 0xFFFFFFFFu : (hi <= 0 ? 0u : (uint32_t)((hi + G - 1) / G));
-    const uint32_t klo = wave_max_any(k_lo), khi = min(wave_min_any(k_hi), Kmax - 1);
-    for (uint32_t k = 0; k + 1 < Kmax; ++k) {
-      if (k == klo && k < khi) {  // the lean stretch: only the block address advances
-        typename S::off_t a = b.src & ~(typename S::off_t)3;
-        uint32_t sel = sel_pay;
-        pin(sel);
-        for (; k < khi; ++k) {
-          const P26 x = p26_from_words(m[0], m[1], m[2], m[3], 1u);
-#pragma unroll
-          for (int l = 0; l < 5; ++l) acc.l[l] += x.l[l];
-          a += 16 * G;
-          load_words_sel<4>(sp, a, sel, m);
-          p26_mul(acc, mG);
-        }
-        const uint32_t nl = khi - klo;
-        i += (int)(G * nl);
-        b.src += 16 * G * nl;
-        b.rem -= (int)(16 * G * nl);
-        if (k + 1 >= Kmax) break;
-      }
-      absorb(b, m);
-      const bool steady = !act || (i >= (int)A && i + G < ct_full_end);
-      i += G;
-      if (!wave_any(!steady)) {
-        b.src += 16 * G;
-        b.rem -= 16 * G;
-        load_words_sel<4>(sp, b.src & ~(typename S::off_t)3, sel_pay, m);
-      } else {
-        b = where(i);
-        load_words<4>(sp, b.src, m);
-      }
-      p26_mul(acc, mG);
-    }
-    absorb(b, m);
-    p26_mul(acc, mlast);
-  }
-#pragma unroll
-  for (int l = 0; l < 5; ++l) acc.l[l] = Gp::sum(acc.l[l]);
-  p26_finish(acc, s, tag);
-}
-
-template <int G, bool SINGLE>
-struct NarrowPolicy {
-  typedef Grp<G> Gp;
-
-  // the one-time key (block 0, group lane 0's keystream words 0..7) on every lane of the group
-  static __device__ __forceinline__ void otk_bcast(const uint32_t (&otk)[8], uint32_t (&r)[4], uint32_t (&s)[4]) {
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      r[k] = Gp::bcast0(otk[k]);
-      s[k] = Gp::bcast0(otk[4 + k]);
-    }
-  }
-
-  // send composite (transmit.rs:625-755) on a narrow tile. Slot order: keystream blocks 1 .. nblk-1
-  // first, the one-time key (block 0) in slot nblk - 1 — made last, so its 8 words are not held
-  // through the loop — then the header-protection block in slot nblk.
-  template <class S, class St>
-  static __device__ __forceinline__ void seal(const S& sp, typename S::off_t pkt, PktCtx& c, const KeyRow* row, int j,
-                                              St& stg) {
-    const mq_pkt_desc& d = c.d;
-    uint32_t key[8];
-    load_key8(row->key, key);
-    const uint32_t aad_len = c.act ? (uint32_t)d.pn_offset + d.pn_len : 0u;
-    const uint32_t P = c.act ? d.len - aad_len - 16 : 0u;
-    const typename S::off_t pay = pkt + aad_len;
-    uint32_t n0 = row->iv[0], n1 = row->iv[1] ^ bswap32((uint32_t)(c.pn >> 32)), n2 = row->iv[2] ^ bswap32((uint32_t)c.pn);
-    // retire the key loads before the LDS-DMA is issued (else the first wait covers the DMA too);
-    // a single-key tile keeps its key in SGPRs
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-      if (SINGLE) key[k] = __builtin_amdgcn_readfirstlane(key[k]);
-      else pin(key[k]);
-    }
-    pin(n0); pin(n1); pin(n2);
-    stg.issue();
-    const uint32_t nblk = 1 + (P + 63) / 64;
-    const bool hp = c.act && !(d.flags & MQ_PKT_NO_HP);
-    // the header-protection block in slot nblk: its sample (payload [4 - pn_len, 20 - pn_len)) is
-    // ciphertext of keystream block 1 (slot 0, iteration 0), so slot nblk must fall in a later
-    // iteration (nblk >= G), and must not reach into the tag (only the MAC produces it)
-    const bool hp_in = hp && P + d.pn_len >= 20u && nblk >= (uint32_t)G;
-    const uint32_t S_ = nblk + (hp_in ? 1u : 0u);
-    const uint32_t Imax = wave_max_any(c.act ? (S_ + G - 1) / G : 0u);
-    uint32_t otk[8] = {0, 0, 0, 0, 0, 0, 0, 0}, m0 = 0, m1 = 0;
-    for (uint32_t it = 0; it < Imax; ++it) {
-      const uint32_t slot = (uint32_t)j + G * it;
-      const bool is_otk = c.act && slot + 1 == nblk;
-      const uint32_t ctr = is_otk ? 0u : slot + 1;  // keystream block of the slot
-      const bool a = c.act && ctr < nblk;            // a keystream block (or the one-time key)
-      const bool is_hp = hp_in && slot == nblk;
-      uint32_t ks[16];
-      if (wave_any(is_hp)) {  // the HP lanes run the HP key on the sample (ciphertext by now)
-        uint32_t smp[4], kh[8], kk[8];
-        load_words<4>(sp, is_hp ? pay + 4u - d.pn_len : pay, smp);
-        load_key8(row->hp, kh);
-#pragma unroll
-        for (int k = 0; k < 8; ++k) kk[k] = is_hp ? kh[k] : key[k];
-        chacha20_block(kk, is_hp ? smp[0] : ctr, is_hp ? smp[1] : n0, is_hp ? smp[2] : n1, is_hp ? smp[3] : n2, ks);
-      } else {
-        chacha20_block(key, ctr, n0, n1, n2, ks);
-      }
-      if (it == 0) {
-        stg.complete();
-        const bool rec = c.act && is_record(d);
-        if (wave_any(rec)) {  // TLS record: header (AAD) and inner content type before any use
-          if (rec && j == 0) write_record_header(sp, pkt, d);
-          wave_sync();
-        }
-      }
-      // the block's raw LDS words after the rounds (not in flight during them: 17 VGPRs fewer)
-      uint32_t w[17];
-      ChaChaPolicy::load_block(sp, pay, a && !is_otk ? ctr : 0u, w);
-      if (is_otk) {
-#pragma unroll
-        for (int k = 0; k < 8; ++k) otk[k] = ks[k];
-      } else if (a) {
-        ChaChaPolicy::store_block(sp, pay, ctr, P, ks, w);
-      }
-      if (is_hp) {
-        m0 = ks[0];
-        m1 = ks[1];
-      }
-      wave_sync();
-    }
-    if (Imax == 0) stg.complete();
-    // the one-time key from its group lane (nblk - 1) % G to the whole group
-    uint32_t r[4], s[4], tag[4];
-    const int src = (int)(threadIdx.x & (kWave - 1)) - j + (int)((nblk + G - 1) % G);
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      r[k] = G == 1 ? otk[k] : (uint32_t)__shfl((int)otk[k], src, kWave);
-      s[k] = G == 1 ? otk[4 + k] : (uint32_t)__shfl((int)otk[4 + k], src, kWave);
-    }
-    poly_tag_g<G>(sp, pkt, pay, aad_len, P, r, s, j, c.act, tag);
-    if (c.act && j == 0) store_words<4>(sp, pay + P, tag);
-    // header protection (transmit.rs:713-738), once the MAC has read the unprotected header
-    const bool late = hp && !hp_in;  // tiny payloads and G > nblk: one more block for the wave
-    if (wave_any(late)) {
-      wave_sync();  // ciphertext and tags are in place
-      uint32_t a0, a1;
-      ChaChaPolicy::hp_mask(sp, pkt + d.pn_offset + 4, row, a0, a1);
-      if (late) {
-        m0 = a0;
-        m1 = a1;
-      }
-    }
-    const int jh = hp_in ? (int)(nblk % G) : 0;  // the group lane holding the mask
-    wave_sync();
-    if (hp && j == jh) apply_hp(sp, pkt, d, m0, m1);
-    wave_sync();
-  }
-
-  // receive composite (recv.rs:340-421 / 953-1025) on a narrow tile: HP removal, decode_pn, verify,
-  // then decrypt
-  template <class S, class St>
-  static __device__ __forceinline__ void open(const S& sp, typename S::off_t pkt, PktCtx& c, const KeyRow* row, int j,
-                                              bool direct, St& stg) {
-    const mq_pkt_desc& d = c.d;
-    stg.issue();
-    uint32_t pn_len = d.pn_len, trunc = 0;
-    uint8_t orig_b0 = 0, b0 = 0;
-    uint32_t orig_pn = 0;
-    const bool hp = c.act && !(d.flags & MQ_PKT_NO_HP);
-    if (c.pre_hp) {
-      if (hp) b0 = header_from_prepass(c, pn_len, trunc);
-    } else {
-      stg.complete();
-      if (wave_any(hp)) {  // every lane of a group computes its packet's mask (one block for the wave)
-        uint32_t m0, m1;
-        ChaChaPolicy::hp_mask(sp, hp ? pkt + d.pn_offset + 4 : pkt, row, m0, m1);
-        if (hp) b0 = header_from_mask(sp, pkt, c, m0, m1, pn_len, trunc);
-      }
-    }
-    uint32_t key[8];
-    load_key8(row->key, key);
-    const uint32_t aad_len = c.act ? (uint32_t)d.pn_offset + pn_len : 0u;
-    const uint32_t P = c.act ? d.len - aad_len - 16 : 0u;
-    const typename S::off_t pay = pkt + aad_len;
-    const uint32_t n0 = row->iv[0], n1 = row->iv[1] ^ bswap32((uint32_t)(c.pn >> 32)),
-                   n2 = row->iv[2] ^ bswap32((uint32_t)c.pn);
-    const uint32_t nblk = 1 + (P + 63) / 64;
-    const uint32_t Imax = wave_max_any(c.act ? (nblk + G - 1) / G : 0u);
-    const uint32_t ctr0 = (uint32_t)j;  // iteration 0 before the MAC (group lane 0: the one-time key)
-    uint32_t ks0[16];
-    chacha20_block(key, ctr0, n0, n1, n2, ks0);
-    if (c.pre_hp) stg.complete();
-    const bool hdr_written = hp && write_unmasked_header(sp, pkt, c, j, b0, pn_len, trunc, orig_b0, orig_pn);
-    wave_sync();
-    uint32_t otk[8], r[4], s[4], tag[4], got[4];
-#pragma unroll
-    for (int k = 0; k < 8; ++k) otk[k] = ks0[k];
-    otk_bcast(otk, r, s);
-    poly_tag_g<G>(sp, pkt, pay, aad_len, P, r, s, j, c.act, tag);
-    load_words<4>(sp, pay + P, got);
-    const uint32_t diff = (tag[0] ^ got[0]) | (tag[1] ^ got[1]) | (tag[2] ^ got[2]) | (tag[3] ^ got[3]);
-    if (c.act && diff != 0) {  // Error::Crypto, buffer left as received
-      c.st = MQ_ERR_CRYPTO;
-      c.act = false;
-    }
-    wave_sync();  // every lane's MAC reads precede any plaintext write
-    if (c.act && ctr0 >= 1 && ctr0 < nblk) {
-      uint32_t w[17];
-      ChaChaPolicy::load_block(sp, pay, ctr0, w);
-      ChaChaPolicy::store_block(sp, pay, ctr0, P, ks0, w);
-    }
-    for (uint32_t it = 1; it < Imax; ++it) {
-      const uint32_t ctr = (uint32_t)j + G * it;
-      const bool a = c.act && ctr < nblk;
-      uint32_t w[17];
-      ChaChaPolicy::load_block(sp, pay, a ? ctr : 0u, w);
-      uint32_t ks[16];
-      chacha20_block(key, ctr, n0, n1, n2, ks);
-      if (a) ChaChaPolicy::store_block(sp, pay, ctr, P, ks, w);
-    }
-    wave_sync();
-    if (direct && hdr_written && !c.act) {  // direct path writes HBM in place: undo the unmask
-      sp.st8(pkt, orig_b0);
-      for (uint32_t b = 0; b < pn_len; ++b) sp.st8(pkt + d.pn_offset + b, (uint8_t)(orig_pn >> (8 * b)));
-    }
-  }
-};
-
 // One narrow tile: entries [e0, e0 + Q) of the batch (index != null: of the list `index`, holes
 // skipped; else descriptor indices), count = the entries' end. Every lane of the wave calls it.
 template <int G, bool OPEN, bool SINGLE>
@@ -910,31 +766,13 @@ __device__ __forceinline__ void narrow_tile(uint8_t* wsm, const KeyRow* __restri
                                             const uint32_t* __restrict__ index, uint8_t* __restrict__ status,
                                             uint64_t* __restrict__ pn_out, const uint2* __restrict__ hpm) {
   constexpr int Q = kWave / G;
-  const int lane = threadIdx.x & (kWave - 1), p = lane / G, j = lane % G;
+  const int lane = threadIdx.x & (kWave - 1), j = lane % G;
   PktCtx c;
-  const uint32_t e = e0 + (uint32_t)p;
-  c.tile = e0 / Q;
-  c.valid = e < count;
-  c.i = c.valid ? (index ? index[e] : e) : 0u;
-  if (c.i == kListHole) { c.valid = false; c.i = 0; }
-  if (c.valid) {
-    c.d = desc[c.i];
-  } else {
-    c.d.offset = 0; c.d.len = 0; c.d.key_id = 0; c.d.pn = 0; c.d.pn_offset = 0; c.d.pn_len = 0;
-    c.d.flags = 0; c.d.reserved = 0;
-  }
-  c.pre_hp = OPEN && hpm != nullptr;
-  c.hm0 = c.hm1 = 0;
-  if (OPEN && hpm && c.valid) {
-    const uint2 m = hpm[c.i];
-    c.hm0 = m.x;
-    c.hm1 = m.y;
-  }
-  c.st = c.valid ? validate<MQ_SUITE_CHACHA20, OPEN, SINGLE>(c.d, kt, n_rows, arena_len) : (int)MQ_ERR_INVALID_ARG;
-  c.act = c.valid && c.st == MQ_OK;
-  c.pn = c.d.pn;
+  const KeyRow* row;
+  if (!tile_ctx<MQ_SUITE_CHACHA20, OPEN, SINGLE, G>(0, kt, n_rows, arena_len, desc, count, index, nullptr, hpm,
+                                                    TilePrefetch{false, 0u, 0u}, c, row, threadIdx.x, e0))
+    return;  // no entry left for this tile
   c.otk = nullptr;
-  const KeyRow* row = SINGLE ? kt : kt + (c.act ? c.d.key_id : 0u);
   Placement pl;
   pl.off = c.act ? c.d.offset : 0;
   pl.len = c.act ? c.d.len : 0u;
@@ -956,15 +794,15 @@ __device__ __forceinline__ void narrow_tile(uint8_t* wsm, const KeyRow* __restri
     NarrowStager<G> stg{wsm, arena, arena_len, total, pl.slot, pl.base(), lane, nch};
     LdsSpace sp{wsm};
     const uint32_t pkt = pl.slot * 16u + pl.head();
-    if (OPEN) NarrowPolicy<G, SINGLE>::template open<LdsSpace>(sp, pkt, c, row, j, false, stg);
-    else NarrowPolicy<G, SINGLE>::template seal<LdsSpace>(sp, pkt, c, row, j, stg);
+    if (OPEN) ChaChaPolicy::open<G, false, SINGLE>(sp, pkt, c, row, j, false, stg);
+    else ChaChaPolicy::seal_narrow<G, SINGLE>(sp, pkt, c, row, j, stg);
     wave_sync();
     narrow_stage_out<G>(wsm, arena, j, c.act, pl);
   } else {
     GlobalSpace sp{arena, arena_len};
     NoStager stg;
-    if (OPEN) NarrowPolicy<G, SINGLE>::template open<GlobalSpace>(sp, pl.off, c, row, j, true, stg);
-    else NarrowPolicy<G, SINGLE>::template seal<GlobalSpace>(sp, pl.off, c, row, j, stg);
+    if (OPEN) ChaChaPolicy::open<G, false, SINGLE>(sp, pl.off, c, row, j, true, stg);
+    else ChaChaPolicy::seal_narrow<G, SINGLE>(sp, pl.off, c, row, j, stg);
   }
   tile_status<OPEN>(c, j, status, pn_out);
 }
@@ -1095,8 +933,8 @@ __device__ __forceinline__ void chacha_tile(uint32_t tb, uint32_t tid, const Key
     LdsSpace sp{wsm};
     MQ_STAMP(tile_id, 1);
     const uint32_t pkt = pl.slot * 16u + pl.head();
-    if (OPEN) ChaChaPolicy::template open<SINGLE, LdsSpace, DmaStager, IMG, W>(sp, pkt, c, row, j, false, stg, pool);
-    else ChaChaPolicy::template seal<SINGLE, LdsSpace, DmaStager, IMG, W>(sp, pkt, c, row, j, stg, pool);
+    if (OPEN) ChaChaPolicy::open<kLanesPerPkt, true, SINGLE, IMG, W>(sp, pkt, c, row, j, false, stg, pool);
+    else ChaChaPolicy::seal<SINGLE, IMG, W>(sp, pkt, c, row, j, stg, pool);
     MQ_STAMP(tile_id, 6);
     wave_sync();
     // a packet that failed to open is never stored: such a tile goes back packet by packet
@@ -1106,8 +944,8 @@ __device__ __forceinline__ void chacha_tile(uint32_t tb, uint32_t tid, const Key
   } else {
     GlobalSpace sp{arena, arena_len};
     NoStager stg;
-    if (OPEN) ChaChaPolicy::template open<SINGLE, GlobalSpace, NoStager, IMG, W>(sp, off, c, row, j, true, stg, pool);
-    else ChaChaPolicy::template seal<SINGLE, GlobalSpace, NoStager, IMG, W>(sp, off, c, row, j, stg, pool);
+    if (OPEN) ChaChaPolicy::open<kLanesPerPkt, true, SINGLE, IMG, W>(sp, off, c, row, j, true, stg, pool);
+    else ChaChaPolicy::seal<SINGLE, IMG, W>(sp, off, c, row, j, stg, pool);
   }
   tile_status<OPEN>(c, j, status, pn_out);
 }
@@ -1438,7 +1276,7 @@ __device__ __forceinline__ void chacha_protect_tile(uint32_t tb, const KeyRow* _
 #endif
     LdsSpace sp{wsm};
     NoStager stg;  // complete(): the wave's image stores are done before any lane reads the image
-    ChaChaPolicy::template seal<SINGLE, LdsSpace>(sp, pl.slot * 16u + pl.head(), c, row, j, stg, pool);
+    ChaChaPolicy::seal<SINGLE>(sp, pl.slot * 16u + pl.head(), c, row, j, stg, pool);
     wave_sync();
     stage_out(wsm, out, lane, c.act, pl);
   } else {
@@ -1446,7 +1284,7 @@ __device__ __forceinline__ void chacha_protect_tile(uint32_t tb, const KeyRow* _
     wave_sync();  // the packets are in HBM before the seal reads them
     GlobalSpace sp{out, out_len};
     NoStager stg;
-    ChaChaPolicy::template seal<SINGLE, GlobalSpace>(sp, c.act ? c.d.offset : 0, c, row, j, stg, pool);
+    ChaChaPolicy::seal<SINGLE>(sp, c.act ? c.d.offset : 0, c, row, j, stg, pool);
   }
   if (c.valid && j == 0) {
     status[c.i] = (uint8_t)c.st;

@@ -337,8 +337,8 @@ __device__ __forceinline__ uint32_t wave_max_any(uint32_t x) {
 }
 __device__ __forceinline__ uint32_t wave_min_any(uint32_t x) { return ~wave_max_any(~x); }
 
-// Lane groups of G = 1, 2, 4 or 8 lanes (one packet per group, lane = G p + j; the narrow ChaCha20
-// tiles, mq_chacha.hip): broadcast of group lane 0, of the last lane, the mirror j -> G-1-j, the sum
+// Lane groups of G = 1, 2, 4 or 8 lanes (one packet per group, lane = G p + j; the ChaCha20 tiles,
+// mq_chacha.hip, octets included): broadcast of group lane 0, of the last lane, the mirror j -> G-1-j, the sum
 // over the group. DPP quad_perm inside a quad (G <= 4), the octet ops above for G = 8.
 template <int G>
 struct Grp {

@@ -416,7 +416,7 @@ __device__ __forceinline__ bool tile_ctx(uint32_t tile_id, const KeyRow* __restr
                                          const uint32_t* __restrict__ index, const uint32_t* __restrict__ n_dev,
                                          const uint2* __restrict__ hpm, const TilePrefetch& pf, PktCtx& c,
                                          const KeyRow*& row, uint32_t tid = threadIdx.x, uint32_t e0 = 0) {
-  static_assert(G == 8 || G == 4 || G == 2, "tiles of 8, 16 or 32 packets");
+  static_assert(G == 8 || G == 4 || G == 2 || G == 1, "tiles of 8, 16, 32 or 64 packets");
   const int lane = tid & (kWave - 1), p = lane / G;
   const uint32_t count = n_dev ? *n_dev : n;
   const uint32_t tile0 = e0 + tile_id * (uint32_t)(kWave / G);  // its first entry
@@ -426,7 +426,7 @@ __device__ __forceinline__ bool tile_ctx(uint32_t tile_id, const KeyRow* __restr
   c.valid = t < count;
   c.pre_hp = OPEN && hpm != nullptr;
   c.hm0 = c.hm1 = 0;
-  if (pf.on) {  // words already in registers
+  if (G > 1 && pf.on) {  // words already in registers (no prefetch layout for 64 packets on one lane each)
     c.i = c.valid ? pf.idx : 0u;
     if (c.i == kListHole) { c.valid = false; c.i = 0; }
     uint32_t w0, w1, w2, w3, w4, w5, w6, w7;

@@ -168,6 +168,53 @@ def test_narrow_failures_match_oracle(orc):
     assert (g_st == o_st).all() and g_out.tobytes() == o_out.tobytes()
 
 
+def exact_batch(L, n_keys=1, pn_len=None, seed=1):
+    """Short-header ChaCha20 packets of exactly the lengths L, packed back to back: pn_len cycling
+    1..4 (or the given one for all), key row i mod n_keys."""
+    L = np.asarray(L, dtype=np.int64)
+    n = len(L)
+    assert (L >= workload.SHORT_HDR + 20).all()  # the header-protection sample fits
+    keys = workload.uniform_keys(CHACHA, n_keys)
+    pl = (1 + np.arange(n) % 4 if pn_len is None else np.full(n, pn_len)).astype(np.uint8)
+    offs = np.concatenate([[0], np.cumsum(L[:-1])]).astype(np.int64)
+    arena = workload.splitmix_bytes(int(offs[-1] + L[-1]), seed=seed)
+    pns = np.uint64(1 << 20) + np.random.default_rng(seed).integers(0, 1 << 30, size=n).astype(np.uint64)
+    po = workload.SHORT_HDR
+    for i in range(n):
+        o = int(offs[i])
+        arena[o] = 0x40 | (int(pl[i]) - 1)
+        for b in range(int(pl[i])):
+            arena[o + po + b] = (int(pns[i]) >> (8 * (int(pl[i]) - 1 - b))) & 0xFF
+    kid = (np.arange(n) % n_keys).astype(np.uint32)
+    args = (offs.astype(np.uint64), L.astype(np.uint32), kid)
+    return (keys, arena, make_descs(*args, pns, np.uint16(po), pl, 0),
+            make_descs(*args, pns - np.uint64(1), np.uint16(po), 0, 0), pns)
+
+
+@pytest.mark.parametrize("n_keys", [1, 3])
+def test_mac_block_boundaries_length_ladder(orc, n_keys):
+    # one packet of every length over 400 consecutive bytes: every MAC block count of every lane
+    # group, and every partial last block, next to neighbours one byte shorter and longer (the
+    # random batches above do not promise to hit each); narrow tiles, octet tiles, G = 8 rounds
+    lo = workload.SHORT_HDR + 20
+    keys, arena, sd, od, pns = exact_batch(np.arange(lo, lo + 401), n_keys, seed=40 + n_keys)
+    roundtrip_vs_oracle(orc, keys, arena, sd, od, pns)
+
+
+@pytest.mark.parametrize("G", [1, 2, 4, 8])
+def test_mac_uniform_waves_at_block_boundaries(orc, G):
+    # 128 packets of one length: whole waves of one geometry, where the MAC's wave-uniform lean
+    # stretch and steady step run; payloads of 16 G k - 1, 16 G k and 16 G k + 1 bytes (k = 2, and
+    # k = 4 where the lean stretch runs on every lane group) end a group's Horner step exactly,
+    # one byte early and one byte late
+    for k in (2, 4):
+        for P in (16 * G * k - 1, 16 * G * k, 16 * G * k + 1):
+            pn_len = 1 + P % 4
+            L = workload.SHORT_HDR + pn_len + P + 16
+            keys, arena, sd, od, pns = exact_batch([L] * 128, 1, pn_len=pn_len, seed=P)
+            roundtrip_vs_oracle(orc, keys, arena, sd, od, pns)
+
+
 @pytest.mark.parametrize("n", [1, 2, 63, 64, 65, 255, 257])
 def test_narrow_counts(orc, n):
     # waves with one packet, exactly full waves, a partial last wave and a partial workgroup
