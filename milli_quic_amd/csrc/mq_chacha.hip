@@ -17,6 +17,7 @@
 #include "mq_opts.h"
 
 #include <cstdlib>
+#include <type_traits>
 
 namespace mq {
 
@@ -237,8 +238,12 @@ struct CcPool {
 
 // IMG: bytes of LDS per wave (kLdsBytes; the long-packet kernels' larger images, chacha_tile);
 // W: waves of the workgroup sharing the pool
-template <bool SINGLE, uint32_t IMG = kLdsBytes, uint32_t W = kCcWaves>
+// R1 (open's pool of a single-key kernel: keystream blocks only, no header-protection entries):
+// the block function takes round one's constant part, computed once per wave (chacha20_round1)
+// Sp: the LDS space of the workgroup's staged tiles (LdsSpace, or LdsSpaceRaw: the raw-dword XOR)
+template <bool SINGLE, uint32_t IMG = kLdsBytes, uint32_t W = kCcWaves, bool R1 = false, class Sp = LdsSpace>
 __device__ __forceinline__ void cc_pool_run(const CcPool& pool, uint32_t tid = threadIdx.x) {
+  static_assert(SINGLE || !R1, "round one is hoisted for wave-uniform keys only");
   constexpr uint32_t kQ = kPktsPerTile * W;  // packets of the workgroup
   static_assert(kQ <= kWave, "one packet per lane in the pool scan");
   const int lane = tid & (kWave - 1);
@@ -250,7 +255,8 @@ __device__ __forceinline__ void cc_pool_run(const CcPool& pool, uint32_t tid = t
   const uint32_t nq = (r0l & 0xffu) + ((r0l >> 8) ? 1u : 0u);
   const uint32_t incl = wave_incl_scan(nq), excl = incl - nq;
   const uint32_t T = lane_u32(incl, kWave - 1);
-  const LdsSpace sp{pool.wg};
+  Sp sp{};
+  sp.base = pool.wg;
   for (uint32_t e0 = kWave * w; e0 < T; e0 += kWave * W) {  // wave-uniform
     const uint32_t e = e0 + (uint32_t)lane;
     uint32_t q = 0;  // the packet of entry e: the last q with excl[q] <= e
@@ -264,11 +270,13 @@ __device__ __forceinline__ void cc_pool_run(const CcPool& pool, uint32_t tid = t
     uint32_t* r = rec(q);
     const uint32_t r0 = r[0], r1 = r[1], pay = r1 & 0x1ffffu, P = r1 >> 17;
     const uint32_t idx = e - eq, pn_len = r0 >> 8;
-    const bool hp = act && idx == (r0 & 0xffu);  // the packet's last entry: its HP block
+    const bool hp = !R1 && act && idx == (r0 & 0xffu);  // the packet's last entry: its HP block
     const uint32_t cb = kCcPoolSlot + idx, o = kKsStride * (cb - 1);
     const KeyRow* row = SINGLE || !act ? pool.kt : pool.kt + r[3];  // an idle lane's record may be stale
     uint32_t key[8];
-    if (SINGLE) {  // both keys wave-uniform (SGPRs); pick per lane
+    if (R1) {
+      load_key8(row->key, key);
+    } else if (SINGLE) {  // both keys wave-uniform (SGPRs); pick per lane
       uint32_t kd[8], kh[8];
       load_key8(row->key, kd);
       load_key8(row->hp, kh);
@@ -277,20 +285,27 @@ __device__ __forceinline__ void cc_pool_run(const CcPool& pool, uint32_t tid = t
     } else {
       load_key8(hp ? row->hp : row->key, key);
     }
-    uint32_t raw[17], smp[4];
-    load_raw<16>(sp, act && !hp ? pay + o : 0u, raw);  // in flight during the rounds
+    XorBlock<16, Sp> x;
+    x.load(sp, act && !hp ? pay + o : 0u);  // LdsSpaceRaw: in flight during the rounds
+    uint32_t smp[4];
     // the sample: 16 bytes at pn_offset + 4 = payload - pn_len + 4 (ciphertext of block 1)
     load_words<4>(sp, hp ? pay + 4u - pn_len : 0u, smp);
     uint32_t ks[16];
-    chacha20_block(key, hp ? smp[0] : cb, hp ? smp[1] : r[4], hp ? smp[2] : r[5], hp ? smp[3] : r[6], ks);
+    if constexpr (R1)
+      chacha20_block(key, cb, r[4], r[5], r[6], chacha20_round1_uniform(key[0], key[1], key[5], row->iv[0]), ks);
+    else
+      chacha20_block(key, hp ? smp[0] : cb, hp ? smp[1] : r[4], hp ? smp[2] : r[5], hp ? smp[3] : r[6], ks);
     if (hp) {
       r[2] = ks[0];
       r[7] = ks[1];
     } else if (act) {
-      xor_words<16>(sp, pay + o, ks, (int)min(64u, P - o), raw);
+      x.apply(sp, pay + o, ks, (int)min(64u, P - o));
     }
   }
 }
+// the pool's space for a tile code running on S (the direct path's tiles pool nothing)
+template <class S> struct PoolSpace { typedef LdsSpace type; };
+template <> struct PoolSpace<LdsSpaceRaw> { typedef LdsSpaceRaw type; };
 
 // The tile code of both layouts: octet tiles (8 lanes per packet, the keystream pool; chacha_tile,
 // chacha_protect_tile) and narrow tiles (G = 1, 2, 4 or 8 lanes per packet, no pool; narrow_tile).
@@ -308,17 +323,18 @@ struct ChaChaPolicy {
       sp.st8(pkt + d.pn_offset + b, (uint8_t)(sp.ld8(pkt + d.pn_offset + b) ^ (uint8_t)(mk >> (8 * b))));
   }
 
-  // raw LDS/HBM dwords under keystream block `ctr` (>= 1): payload [64(ctr-1), min(64 ctr, P))
+  // keystream block `ctr` (>= 1) covers payload [64(ctr-1), min(64 ctr, P)). load_block: the raw
+  // HBM dwords under it (direct path; a staged tile XORs in LDS and loads nothing)
   template <class S>
   static __device__ __forceinline__ void load_block(const S& sp, typename S::off_t pay, uint32_t ctr,
-                                                    uint32_t (&raw)[17]) {
-    load_raw<16>(sp, pay + kKsStride * (ctr > 0 ? ctr - 1 : 0), raw);
+                                                    XorBlock<16, S>& x) {
+    x.load(sp, pay + kKsStride * (ctr > 0 ? ctr - 1 : 0));
   }
   template <class S>
   static __device__ __forceinline__ void store_block(const S& sp, typename S::off_t pay, uint32_t ctr, uint32_t P,
-                                                     const uint32_t (&ks)[16], const uint32_t (&raw)[17]) {
+                                                     const uint32_t (&ks)[16], const XorBlock<16, S>& x) {
     const uint32_t o = kKsStride * (ctr - 1);
-    xor_words<16>(sp, pay + o, ks, (int)min(64u, P - o), raw);
+    x.apply(sp, pay + o, ks, (int)min(64u, P - o));
   }
 
   static __device__ __forceinline__ void store_otk(uint32_t* otk, const uint32_t (&ks)[16]) {
@@ -407,7 +423,8 @@ struct ChaChaPolicy {
   // iteration ctr / 8 (ctr 0 = the Poly1305 key); with the pool, blocks >= 16 and the
   // header-protection block (its sample is ciphertext of block 1) run in the workgroup's pool
   // before the MACs, and the mask is applied once the MAC has read the unprotected header.
-  template <bool SINGLE, uint32_t IMG = kLdsBytes, uint32_t W = kCcWaves, class S, class St>
+  // R1: round one's wave-uniform part hoisted (single-key kernels; chacha_tile says which)
+  template <bool SINGLE, uint32_t IMG = kLdsBytes, uint32_t W = kCcWaves, bool R1 = false, class S, class St>
   static __device__ __forceinline__ void seal(const S& sp, typename S::off_t pkt, PktCtx& c, const KeyRow* row, int j,
                                               St& stg, const CcPool& pool) {
     const mq_pkt_desc& d = c.d;
@@ -418,13 +435,25 @@ struct ChaChaPolicy {
     stg.issue();  // packet bytes stream into LDS while the first keystream block is computed
     const uint32_t kst = pool.on ? min(nblk, kCcPoolSlot) : nblk;  // blocks of this wave's own slots
     const uint32_t Imax = wave_max_u32(c.act ? (kst + kLanesPerPkt - 1) / kLanesPerPkt : 0u);
+    // single key: the key and nonce word 0 are wave-uniform, so is round one's part of them
+    ChaChaRound1 r1{};
+    static_assert(SINGLE || !R1, "round one is hoisted for wave-uniform keys only");
+    if constexpr (R1) r1 = chacha20_round1_uniform(k.key[0], k.key[1], k.key[5], k.n0);
     for (uint32_t it = 0; it < Imax; ++it) {
       const uint32_t ctr = (uint32_t)j + kLanesPerPkt * it;
       const bool a = c.act && ctr < kst;
-      uint32_t w[17];
-      if (it > 0) load_block(sp, pay, a ? ctr : 0u, w);  // LDS reads in flight during the block function
+      XorBlock<16, S> w;
+      if (it > 0) load_block(sp, pay, a ? ctr : 0u, w);  // direct path: in flight during the block function
       uint32_t ks[16];
-      chacha20_block(k.key, ctr, k.n0, k.n1, k.n2, ks);
+      if constexpr (R1) {
+        // the nonce words opaque per iteration: hipcc would otherwise compute columns 2 and 3 of
+        // round one once for both iterations and hold them (8 VGPRs: 128 and 20 B of scratch)
+        uint32_t m1 = k.n1, m2 = k.n2;
+        pin(m1); pin(m2);
+        chacha20_block(k.key, ctr, k.n0, m1, m2, r1, ks);
+      } else {
+        chacha20_block(k.key, ctr, k.n0, k.n1, k.n2, ks);
+      }
       if (it == 0) {
         stg.complete();
         MQ_STAMP(c.tile, 2);
@@ -457,7 +486,7 @@ struct ChaChaPolicy {
       }
     }
     __syncthreads();  // every wave's records
-    cc_pool_run<SINGLE, IMG, W>(pool);
+    cc_pool_run<SINGLE, IMG, W, false, typename PoolSpace<S>::type>(pool);
     __syncthreads();  // every pooled block (and mask) is in place before any MAC reads it
     MQ_STAMP(c.tile, 3);
     uint32_t tag[4];
@@ -518,8 +547,8 @@ struct ChaChaPolicy {
           wave_sync();
         }
       }
-      // the block's raw LDS words after the rounds (not in flight during them: 17 VGPRs fewer)
-      uint32_t w[17];
+      // direct path: the block's raw words after the rounds (not in flight during them: 17 VGPRs fewer)
+      XorBlock<16, S> w;
       load_block(sp, pay, a && !is_otk ? ctr : 0u, w);
       if (is_otk) {
 #pragma unroll
@@ -553,7 +582,9 @@ struct ChaChaPolicy {
   // decrypt. G lanes per packet. POOL (the octet tiles of chacha_tile): the one-time key goes
   // through the packet's LDS scratch and keystream blocks >= 16 to the workgroup's pool, both
   // barriers included; else (narrow tiles) the key travels by DPP and the wave runs every block.
-  template <int G, bool POOL, bool SINGLE, uint32_t IMG = kLdsBytes, uint32_t W = kCcWaves, class S, class St>
+  // R1: round one's wave-uniform part hoisted (single-key octet kernels; chacha_tile says which)
+  template <int G, bool POOL, bool SINGLE, uint32_t IMG = kLdsBytes, uint32_t W = kCcWaves, bool R1 = false, class S,
+            class St>
   static __device__ __forceinline__ void open(const S& sp, typename S::off_t pkt, PktCtx& c, const KeyRow* row, int j,
                                               bool direct, St& stg, const CcPool& pool = CcPool{}) {
     typedef Grp<G> Gp;
@@ -587,8 +618,14 @@ struct ChaChaPolicy {
     const uint32_t Cmax = Gp::wave_max(c.act ? (nblk + G - 1) / G : 0u);
     // first keystream block of every lane is computed before the MAC (group lane 0: one-time key)
     const uint32_t ctr0 = (uint32_t)j;
+    // octet tiles of a single-key kernel: round one's wave-uniform part once for every block
+    static_assert((POOL && SINGLE) || !R1, "round one is hoisted for wave-uniform keys only");
+    constexpr bool kR1 = R1;
+    ChaChaRound1 r1{};
+    if constexpr (kR1) r1 = chacha20_round1_uniform(row->key[0], row->key[1], row->key[5], row->iv[0]);
     uint32_t ks0[16];
-    chacha20_block(key, ctr0, n0, n1, n2, ks0);
+    if constexpr (kR1) chacha20_block(key, ctr0, n0, n1, n2, r1, ks0);
+    else chacha20_block(key, ctr0, n0, n1, n2, ks0);
     if (c.pre_hp) stg.complete();
     if (POOL) MQ_STAMP(c.tile, 2);
     const bool hdr_written = hp && write_unmasked_header(sp, pkt, c, j, b0, pn_len, trunc, orig_b0, orig_pn);
@@ -616,7 +653,7 @@ struct ChaChaPolicy {
     wave_sync();  // every lane's MAC reads precede any plaintext write
     if (POOL) MQ_STAMP(c.tile, 4);
     if (c.act && ctr0 >= 1 && ctr0 < nblk) {
-      uint32_t w[17];
+      XorBlock<16, S> w;
       load_block(sp, pay, ctr0, w);
       store_block(sp, pay, ctr0, P, ks0, w);
     }
@@ -624,10 +661,11 @@ struct ChaChaPolicy {
     for (uint32_t it = 1; it < Cown; ++it) {
       const uint32_t ctr = (uint32_t)j + G * it;
       const bool a = c.act && ctr < nblk;
-      uint32_t w[17];
+      XorBlock<16, S> w;
       load_block(sp, pay, a ? ctr : 0u, w);
       uint32_t ks[16];
-      chacha20_block(key, ctr, n0, n1, n2, ks);
+      if constexpr (kR1) chacha20_block(key, ctr, n0, n1, n2, r1, ks);
+      else chacha20_block(key, ctr, n0, n1, n2, ks);
       if (a) store_block(sp, pay, ctr, P, ks, w);
     }
     if constexpr (POOL) {
@@ -641,7 +679,7 @@ struct ChaChaPolicy {
         }
       }
       __syncthreads();  // every wave's MAC has read its ciphertext
-      cc_pool_run<SINGLE, IMG, W>(pool);
+      cc_pool_run<SINGLE, IMG, W, R1, typename PoolSpace<S>::type>(pool);
       __syncthreads();
       MQ_STAMP(c.tile, 5);
     } else {
@@ -671,7 +709,7 @@ struct ChaChaPolicy {
 // lane j. Used by flat ChaCha20 batches of short packets (mq_launch_chacha picks the narrow kernel
 // by the arena's bytes per packet) and by the short length classes of a mixed batch's ChaCha20 list
 // (mq_partition.hip regions).
-constexpr uint32_t kNarrowSlack = 64;                              // load_raw overreach past an image
+constexpr uint32_t kNarrowSlack = 64;                              // xor_words overreach past an image
 constexpr uint32_t kNarrowChunks = (kLdsBytes - kNarrowSlack) / 16;  // 636
 
 template <int G>
@@ -759,7 +797,8 @@ __device__ __forceinline__ void narrow_stage_out(const uint8_t* smem, uint8_t* a
 
 // One narrow tile: entries [e0, e0 + Q) of the batch (index != null: of the list `index`, holes
 // skipped; else descriptor indices), count = the entries' end. Every lane of the wave calls it.
-template <int G, bool OPEN, bool SINGLE>
+// RAW: the keystream XOR of staged tiles in its raw-dword form (LdsSpaceRaw; chacha_tile)
+template <int G, bool OPEN, bool SINGLE, bool RAW = false>
 __device__ __forceinline__ void narrow_tile(uint8_t* wsm, const KeyRow* __restrict__ kt, uint32_t n_rows,
                                             uint8_t* __restrict__ arena, uint64_t arena_len,
                                             const mq_pkt_desc* __restrict__ desc, uint32_t e0, uint32_t count,
@@ -792,7 +831,8 @@ __device__ __forceinline__ void narrow_tile(uint8_t* wsm, const KeyRow* __restri
   if (total <= kNarrowChunks) {
     pl.slot = incl - nch - pad;
     NarrowStager<G> stg{wsm, arena, arena_len, total, pl.slot, pl.base(), lane, nch};
-    LdsSpace sp{wsm};
+    typename std::conditional<RAW, LdsSpaceRaw, LdsSpace>::type sp{};
+    sp.base = wsm;
     const uint32_t pkt = pl.slot * 16u + pl.head();
     if (OPEN) ChaChaPolicy::open<G, false, SINGLE>(sp, pkt, c, row, j, false, stg);
     else ChaChaPolicy::seal_narrow<G, SINGLE>(sp, pkt, c, row, j, stg);
@@ -824,7 +864,7 @@ using namespace mq;
 // A partition list's narrow regions (mq_partition.hip: reg = tiles of G = 8, 4, 2, 1, then the first
 // entries of the G = 4, 2, 1 regions): list tile u >= T8 is narrow tile u - T8 of the G = 4 region,
 // and so on. Runs it, if there is one.
-template <bool OPEN, bool SINGLE>
+template <bool OPEN, bool SINGLE, bool RAW>
 __device__ __forceinline__ void chacha_narrow_list(uint8_t* wsm, uint32_t u, const uint32_t* __restrict__ reg,
                                                    const KeyRow* __restrict__ kt, uint32_t n_rows,
                                                    uint8_t* __restrict__ arena, uint64_t arena_len,
@@ -835,19 +875,19 @@ __device__ __forceinline__ void chacha_narrow_list(uint8_t* wsm, uint32_t u, con
   if (u < T8) return;
   uint32_t v = u - T8;
   if (v < T4) {
-    narrow_tile<4, OPEN, SINGLE>(wsm, kt, n_rows, arena, arena_len, desc, R4 + 16 * v, R4 + 16 * T4, index, status,
+    narrow_tile<4, OPEN, SINGLE, RAW>(wsm, kt, n_rows, arena, arena_len, desc, R4 + 16 * v, R4 + 16 * T4, index, status,
                                  pn_out, hpm);
     return;
   }
   v -= T4;
   if (v < T2) {
-    narrow_tile<2, OPEN, SINGLE>(wsm, kt, n_rows, arena, arena_len, desc, R2 + 32 * v, R2 + 32 * T2, index, status,
+    narrow_tile<2, OPEN, SINGLE, RAW>(wsm, kt, n_rows, arena, arena_len, desc, R2 + 32 * v, R2 + 32 * T2, index, status,
                                  pn_out, hpm);
     return;
   }
   v -= T2;
   if (v < T1)
-    narrow_tile<1, OPEN, SINGLE>(wsm, kt, n_rows, arena, arena_len, desc, R1 + 64 * v, R1 + 64 * T1, index, status,
+    narrow_tile<1, OPEN, SINGLE, RAW>(wsm, kt, n_rows, arena, arena_len, desc, R1 + 64 * v, R1 + 64 * T1, index, status,
                                  pn_out, hpm);
 }
 
@@ -869,6 +909,14 @@ __device__ __forceinline__ void chacha_tile(uint32_t tb, uint32_t tid, const Key
   uint8_t* wsm = smem + w * IMG;
   const int lane = tid & (kWave - 1), p = lane / kLanesPerPkt, j = lane % kLanesPerPkt;
   const uint32_t tile_id = tb * W + w;
+  // The multi-key seal kernels over partition lists (one-shot and persistent grid) keep the raw-dword
+  // XOR: the atomic form costs them scratch (12 and 4 more bytes per lane)
+  constexpr bool kRaw = !OPEN && !SINGLE && (LIST || !SPAN);
+  typedef typename std::conditional<kRaw, LdsSpaceRaw, LdsSpace>::type Sp;
+  // Round one's wave-uniform part is hoisted in the single-key kernels, but not in the persistent
+  // list kernels (SPAN = false) nor in the fused protect tile: there it costs scratch (seal list
+  // 40 -> 44 B per lane, open list 0 -> 20, protect 0 -> 8)
+  constexpr bool kR1 = SINGLE && SPAN;
   const bool span_ok = SPAN && (n_rows & kCcNoSpan) == 0;
   n_rows &= ~kCcNoSpan;
   PktCtx c;
@@ -884,18 +932,18 @@ __device__ __forceinline__ void chacha_tile(uint32_t tb, uint32_t tid, const Key
     // past the batch (list capacities exceed the count): a whole workgroup leaves at once, a
     // wave of a live workgroup only joins its barriers and pool
     if (tb * W * kPktsPerTile >= (n_dev ? *n_dev : n)) {  // workgroup-uniform
-      if (LIST) chacha_narrow_list<OPEN, SINGLE>(wsm, tile_id, reg, kt, n_rows, arena, arena_len, desc, index, status,
+      if (LIST) chacha_narrow_list<OPEN, SINGLE, kRaw>(wsm, tile_id, reg, kt, n_rows, arena, arena_len, desc, index, status,
                                                  pn_out, hpm);
       return;
     }
     if (LIST) {  // this wave's narrow tile, before the barriers (its records are reset after it)
-      chacha_narrow_list<OPEN, SINGLE>(wsm, tile_id, reg, kt, n_rows, arena, arena_len, desc, index, status, pn_out,
+      chacha_narrow_list<OPEN, SINGLE, kRaw>(wsm, tile_id, reg, kt, n_rows, arena, arena_len, desc, index, status, pn_out,
                                        hpm);
       wave_sync();
     }
     if (j == 0) pool.rec[0] = 0;
     __syncthreads();
-    cc_pool_run<SINGLE, IMG, W>(pool, tid);
+    cc_pool_run<SINGLE, IMG, W, OPEN && kR1, Sp>(pool, tid);
     __syncthreads();
     return;
   }
@@ -930,11 +978,12 @@ __device__ __forceinline__ void chacha_tile(uint32_t tb, uint32_t tid, const Key
     const bool in_span = c.act && (((uint32_t)off | pl.len) & 15u) == 0 && off == lane_u64(off, 0) + 16u * pl.slot;
     const bool span = span_ok && pad == 0 && !wave_any(!in_span);
     DmaStager stg{wsm, arena, arena_len, lane, j, pl, span ? total : 0u};
-    LdsSpace sp{wsm};
+    Sp sp{};
+    sp.base = wsm;
     MQ_STAMP(tile_id, 1);
     const uint32_t pkt = pl.slot * 16u + pl.head();
-    if (OPEN) ChaChaPolicy::open<kLanesPerPkt, true, SINGLE, IMG, W>(sp, pkt, c, row, j, false, stg, pool);
-    else ChaChaPolicy::seal<SINGLE, IMG, W>(sp, pkt, c, row, j, stg, pool);
+    if (OPEN) ChaChaPolicy::open<kLanesPerPkt, true, SINGLE, IMG, W, kR1>(sp, pkt, c, row, j, false, stg, pool);
+    else ChaChaPolicy::seal<SINGLE, IMG, W, kR1>(sp, pkt, c, row, j, stg, pool);
     MQ_STAMP(tile_id, 6);
     wave_sync();
     // a packet that failed to open is never stored: such a tile goes back packet by packet
@@ -944,8 +993,8 @@ __device__ __forceinline__ void chacha_tile(uint32_t tb, uint32_t tid, const Key
   } else {
     GlobalSpace sp{arena, arena_len};
     NoStager stg;
-    if (OPEN) ChaChaPolicy::open<kLanesPerPkt, true, SINGLE, IMG, W>(sp, off, c, row, j, true, stg, pool);
-    else ChaChaPolicy::seal<SINGLE, IMG, W>(sp, off, c, row, j, stg, pool);
+    if (OPEN) ChaChaPolicy::open<kLanesPerPkt, true, SINGLE, IMG, W, kR1>(sp, off, c, row, j, true, stg, pool);
+    else ChaChaPolicy::seal<SINGLE, IMG, W, kR1>(sp, off, c, row, j, stg, pool);
   }
   tile_status<OPEN>(c, j, status, pn_out);
 }

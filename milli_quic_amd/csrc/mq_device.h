@@ -82,6 +82,10 @@ struct LdsSpace {
   }
 };
 
+// The same LDS whose keystream XOR stays the raw-dword read-modify-write (XorBlock's general form),
+// for the kernels in which the atomic form costs registers (mq_chacha.hip chacha_tile)
+struct LdsSpaceRaw : LdsSpace {};
+
 struct GlobalSpace {
   uint8_t* base;
   uint64_t len;  // reads at or beyond len return 0 (never fault)
@@ -137,6 +141,11 @@ __device__ __forceinline__ uint32_t range_mask(int lo, int hi) {
   return h & ~l;
 }
 
+__device__ __forceinline__ uint32_t byte_mask(int rem, int k) {  // keep bytes < rem of word k
+  int r = rem - 4 * k;
+  return r >= 4 ? 0xffffffffu : (r <= 0 ? 0u : ((1u << (8 * r)) - 1u));
+}
+
 // Raw memory dwords covering N payload words at byte address `a` (for xor_words).
 template <int N, class S>
 __device__ __forceinline__ void load_raw(const S& sp, typename S::off_t a, uint32_t (&raw)[N + 1]) {
@@ -174,6 +183,52 @@ __device__ __forceinline__ void xor_words(const S& sp, typename S::off_t a, cons
   }
 }
 
+// The same in LDS, where an atomic XOR (ds_xor_b32, no return) does the read-modify-write in
+// memory: no raw dwords, one path for every length. Keystream past `len` is zeroed (only when
+// some lane of the wave holds a partial block), the words are realigned to the N + 1 memory dwords
+// and each is XORed in: zero bytes change nothing, and the atomic is race-free against whoever
+// updates the other bytes of a dword (the neighbouring lane, the neighbouring packet, the pool).
+// Touches all N + 1 dwords from a & ~3 whatever `len` is (as load_raw reads them).
+template <int N>
+__device__ __forceinline__ void xor_words(const LdsSpace& sp, uint32_t a, const uint32_t (&ks)[N], int len) {
+  const uint32_t b = a & ~3u, sel = sel_store(a & 3u);
+  uint32_t k[N];
+#pragma unroll
+  for (int m = 0; m < N; ++m) k[m] = ks[m];
+  if (__builtin_amdgcn_ballot_w64(len < 4 * N) != 0) {  // wave-uniform: off the whole-block path
+    // word m keeps all its bytes when m < len / 4 and the low len % 4 of them when m == len / 4.
+    // Bit i of `upto` is set for i <= len / 4; a signed 1-bit field extract spreads bit m + 1
+    // (m < len / 4) or bit m (m <= len / 4) over a word: three VALU a word
+    const uint32_t upto = (2u << (len >> 2)) - 1u, part = (1u << (8 * (len & 3))) - 1u;
+#pragma unroll
+    for (int m = 0; m < N; ++m) {
+      const uint32_t lt = (uint32_t)__builtin_amdgcn_sbfe((int)upto, m + 1, 1);
+      const uint32_t le = (uint32_t)__builtin_amdgcn_sbfe((int)upto, m, 1);
+      k[m] = __builtin_amdgcn_bitop3_b32(k[m], lt, le & part, 0xE0);  // k & (lt | (le & part))
+    }
+  }
+#pragma unroll
+  for (int m = 0; m <= N; ++m) sp.xor32(b + 4 * m, perm(m < N ? k[m] : 0u, m > 0 ? k[m - 1] : 0u, sel));
+}
+
+// What a keystream XOR needs of the memory under its block: the raw dwords on the direct path
+// (loaded before the rounds, in flight during them), nothing in LDS.
+template <int N, class S>
+struct XorBlock {
+  uint32_t raw[N + 1];
+  __device__ __forceinline__ void load(const S& sp, typename S::off_t a) { load_raw<N>(sp, a, raw); }
+  __device__ __forceinline__ void apply(const S& sp, typename S::off_t a, const uint32_t (&ks)[N], int len) const {
+    xor_words<N>(sp, a, ks, len, raw);
+  }
+};
+template <int N>
+struct XorBlock<N, LdsSpace> {
+  __device__ __forceinline__ void load(const LdsSpace&, uint32_t) {}
+  __device__ __forceinline__ void apply(const LdsSpace& sp, uint32_t a, const uint32_t (&ks)[N], int len) const {
+    xor_words<N>(sp, a, ks, len);
+  }
+};
+
 // Write N payload-aligned words at byte address `a` (any alignment), preserving the bytes of
 // the two edge dwords outside the range. Only for a single writer per packet (e.g. the tag,
 // written by lane j == 0 after every keystream update of its packet).
@@ -199,11 +254,6 @@ __device__ __forceinline__ void store_words(const S& sp, typename S::off_t a, co
 // Keep the compiler from sinking the wait for `x`'s load past this point (used to retire the
 // key loads before LDS-DMA is issued: hipcc would otherwise wait vmcnt(0) on the DMA too).
 __device__ __forceinline__ void pin(uint32_t& x) { asm volatile("" : "+v"(x)); }
-
-__device__ __forceinline__ uint32_t byte_mask(int rem, int k) {  // keep bytes < rem of word k
-  int r = rem - 4 * k;
-  return r >= 4 ? 0xffffffffu : (r <= 0 ? 0u : ((1u << (8 * r)) - 1u));
-}
 
 __device__ __forceinline__ uint32_t bswap32(uint32_t x) { return __builtin_bswap32(x); }
 
@@ -441,6 +491,60 @@ __device__ __forceinline__ void chacha20_block(const uint32_t (&key)[8], uint32_
   uint32_t x12 = ctr, x13 = n0, x14 = n1, x15 = n2;
 #pragma unroll 2
   for (int i = 0; i < 10; ++i) {
+    MQ_QR(x0, x4, x8, x12) MQ_QR(x1, x5, x9, x13) MQ_QR(x2, x6, x10, x14) MQ_QR(x3, x7, x11, x15)
+    MQ_QR(x0, x5, x10, x15) MQ_QR(x1, x6, x11, x12) MQ_QR(x2, x7, x8, x13) MQ_QR(x3, x4, x9, x14)
+  }
+  out[0] = x0 + 0x61707865u; out[1] = x1 + 0x3320646eu; out[2] = x2 + 0x79622d32u;
+  out[3] = x3 + 0x6b206574u;
+  out[4] = x4 + key[0]; out[5] = x5 + key[1]; out[6] = x6 + key[2]; out[7] = x7 + key[3];
+  out[8] = x8 + key[4]; out[9] = x9 + key[5]; out[10] = x10 + key[6]; out[11] = x11 + key[7];
+  out[12] = x12 + ctr; out[13] = x13 + n0; out[14] = x14 + n1; out[15] = x15 + n2;
+}
+
+// What the first column round computes from the key and nonce word 0 alone (no counter, no packet
+// number: QUIC's nonce leaves iv[0] as it is): x0 + x4 and the whole quarter-round of column 1.
+// A single-key kernel computes it once per wave from wave-uniform values (scalar registers).
+struct ChaChaRound1 { uint32_t a0, x1, x5, x9, x13; };
+__device__ __forceinline__ ChaChaRound1 chacha20_round1(uint32_t k0, uint32_t k1, uint32_t k5, uint32_t n0) {
+  ChaChaRound1 h;
+  h.a0 = 0x61707865u + k0;
+  h.x1 = 0x3320646eu; h.x5 = k1; h.x9 = k5; h.x13 = n0;
+  MQ_QR(h.x1, h.x5, h.x9, h.x13)
+  return h;
+}
+// The same for wave-uniform inputs, into scalar registers. (hipcc has no scalar rotate: left to
+// itself it runs the quarter-round on the VALU and holds the five words in VGPRs.)
+__device__ __forceinline__ ChaChaRound1 chacha20_round1_uniform(uint32_t k0, uint32_t k1, uint32_t k5, uint32_t n0) {
+  ChaChaRound1 h = chacha20_round1(k0, k1, k5, n0);
+  h.a0 = __builtin_amdgcn_readfirstlane(h.a0);
+  h.x1 = __builtin_amdgcn_readfirstlane(h.x1);
+  h.x5 = __builtin_amdgcn_readfirstlane(h.x5);
+  h.x9 = __builtin_amdgcn_readfirstlane(h.x9);
+  h.x13 = __builtin_amdgcn_readfirstlane(h.x13);
+  return h;
+}
+// chacha20_block with that part of round one taken from `h` = chacha20_round1(key[0], key[1],
+// key[5], n0): 13 VALU fewer per block when h sits in scalar registers.
+__device__ __forceinline__ void chacha20_block(const uint32_t (&key)[8], uint32_t ctr,
+                                               uint32_t n0, uint32_t n1, uint32_t n2,
+                                               const ChaChaRound1& h, uint32_t (&out)[16]) {
+#if MQ_PROF_SKIP & 1  // phase-cost diagnostic build only (tools/phase_cost.py): no rounds
+  chacha20_block(key, ctr, n0, n1, n2, out);
+  return;
+#endif
+  uint32_t x0 = h.a0, x1 = h.x1, x2 = 0x79622d32u, x3 = 0x6b206574u;
+  uint32_t x4 = key[0], x5 = h.x5, x6 = key[2], x7 = key[3];
+  uint32_t x8 = key[4], x9 = h.x9, x10 = key[6], x11 = key[7];
+  uint32_t x12 = ctr, x13 = h.x13, x14 = n1, x15 = n2;
+  // column 0 behind its first addition
+  x12 ^= x0; x12 = rotl(x12, 16);
+  x8 += x12; x4 ^= x8; x4 = rotl(x4, 12);
+  x0 += x4; x12 ^= x0; x12 = rotl(x12, 8);
+  x8 += x12; x4 ^= x8; x4 = rotl(x4, 7);
+  MQ_QR(x2, x6, x10, x14) MQ_QR(x3, x7, x11, x15)
+  MQ_QR(x0, x5, x10, x15) MQ_QR(x1, x6, x11, x12) MQ_QR(x2, x7, x8, x13) MQ_QR(x3, x4, x9, x14)
+#pragma unroll 3
+  for (int i = 1; i < 10; ++i) {
     MQ_QR(x0, x4, x8, x12) MQ_QR(x1, x5, x9, x13) MQ_QR(x2, x6, x10, x14) MQ_QR(x3, x7, x11, x15)
     MQ_QR(x0, x5, x10, x15) MQ_QR(x1, x6, x11, x12) MQ_QR(x2, x7, x8, x13) MQ_QR(x3, x4, x9, x14)
   }
