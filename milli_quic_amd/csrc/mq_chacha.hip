@@ -55,10 +55,14 @@ struct OtkRegs {
 // CT||pad16||LE64(len AAD)||LE64(len CT)), G lanes per packet (8: an octet tile, 1 / 2 / 4: narrow
 // tiles): group lane j takes MAC blocks G k + j - z, Horner with r^G, one final multiply by
 // r^(G-j), then the group sum. Every lane of the group returns the same tag.
+// The edge steps of the octet form (kEdge below: the lean stretch up to the last whole block, the
+// general absorb's single byte count) are not taken by the narrow lane groups G < 8: their batches
+// (64- and 256-B packets) measured 0.6 % slower with them (profiles/r09_ab_len_sweep_all_groups.txt).
 template <int G, class S, class K>
 __device__ __forceinline__ void poly_tag(const S& sp, typename S::off_t pkt, typename S::off_t pay, uint32_t aad_len,
                                          uint32_t ct_len, const K& otk, int j, bool act, uint32_t (&tag)[4]) {
   typedef Grp<G> Gp;
+  constexpr bool kEdge = G == 8;
   uint32_t rk[4], s[4];
 #if MQ_PROF_SKIP & 2
   otk.s(s);
@@ -98,12 +102,13 @@ __device__ __forceinline__ void poly_tag(const S& sp, typename S::off_t pkt, typ
   }
   const P26m mG = p26_mult(rG), mlast = p26_mult(rj);
 
-  const uint32_t A = (aad_len + 15) >> 4, T = (ct_len + 15) >> 4, nb = A + T + 1;
-  const uint32_t K_ = (nb + G - 1) / G;
+  const PolyGeom geo = poly_geom<G>(aad_len, ct_len);  // the schedule: mq_poly_sched.h
+  const uint32_t A = geo.A, T = geo.T;
   // per-packet values are group-uniform: the group reductions
-  const uint32_t Kmax = Gp::wave_max(act ? K_ : 0u);
+  const uint32_t Kmax = Gp::wave_max(act ? geo.K : 0u);
   // prepend zero blocks (no 2^128 bit) so every packet of the wave runs exactly Kmax steps
-  const int z = (int)(G * Kmax) - (int)nb;
+  const PolyLean ln = poly_lean<G, kEdge>(A, geo.nb, ct_len, Kmax, act);
+  const int z = ln.z;
   P26 acc;
 #pragma unroll
   for (int l = 0; l < 5; ++l) acc.l[l] = 0;
@@ -111,21 +116,29 @@ __device__ __forceinline__ void poly_tag(const S& sp, typename S::off_t pkt, typ
   // MAC block i = G k + j - z of this lane: where it lives, how many of its bytes are real
   struct Blk { typename S::off_t src; int rem; bool pre, lens; };
   auto where = [&](int i) {
+    const PolyBlk pb = poly_blk(A, T, aad_len, ct_len, i);
     Blk b;
-    const bool aad = i < (int)A;
-    b.pre = i < 0;  // prepended zero block
-    b.lens = i == (int)(A + T);
-    b.src = aad ? pkt + 16 * (uint32_t)max(i, 0) : pay + 16 * (uint32_t)(i - (int)A);
-    b.rem = aad ? (int)aad_len - 16 * i : (int)ct_len - 16 * (i - (int)A);
+    b.pre = pb.pre;
+    b.lens = pb.lens;
+    b.src = pb.aad ? pkt + pb.off : pay + pb.off;
+    b.rem = pb.rem;
     if (b.pre || b.lens) b.src = pkt;
     return b;
   };
   auto absorb = [&](const Blk& b, uint32_t (&m)[4]) {
     // wave-uniform fast path: every active lane holds a whole AAD / ciphertext block
-    if (wave_any(act && (b.pre || b.lens || b.rem < 16))) {
+    if (!kEdge) {
+      if (wave_any(act && (b.pre || b.lens || b.rem < 16))) {
 #pragma unroll
-      for (int w = 0; w < 4; ++w) m[w] &= byte_mask(b.pre ? 0 : b.rem, w);
-      if (b.lens) { m[0] = aad_len; m[1] = 0; m[2] = ct_len; m[3] = 0; }
+        for (int w = 0; w < 4; ++w) m[w] &= byte_mask(b.pre ? 0 : b.rem, w);
+        if (b.lens) { m[0] = aad_len; m[1] = 0; m[2] = ct_len; m[3] = 0; }
+      }
+    } else if (wave_any(act && (b.pre || b.lens || b.rem < 16))) {
+      // one byte count per lane: nothing of a prepended block or of the lengths block's slot, whose
+      // two non-zero words then go in
+      keep_bytes<4>(m, b.pre || b.lens ? 0 : min(max(b.rem, 0), 16));
+      m[0] = b.lens ? aad_len : m[0];
+      m[2] = b.lens ? ct_len : m[2];
     }
     const P26 x = p26_from_words(m[0], m[1], m[2], m[3], b.pre ? 0u : 1u);
 #pragma unroll
@@ -140,15 +153,16 @@ __device__ __forceinline__ void poly_tag(const S& sp, typename S::off_t pkt, typ
     // blocks on (src + 16 G, payload alignment fixed), so the address and realignment selector
     // need no per-step recomputation
     const uint32_t sel_pay = sel_load((uint32_t)(pay & 3));
-    const int ct_full_end = (int)A + (int)(ct_len >> 4);  // first index past the whole CT blocks
-    // lean steps k in [k_lo, k_hi): every active lane absorbs a whole ciphertext block and loads
-    // the next whole one (G k + j - z in [A, ct_full_end - G)), so no masks, 2^128 bit selects
-    // or address recomputation
-    const int zA = (int)A + z;
-    const uint32_t k_lo = act ? (uint32_t)((zA + G - 1) / G) : 0u;
-    const int hi = ct_full_end + z - 2 * G + 1;  // lean iff G k + 2G - 1 - z < ct_full_end
-    const uint32_t k_hi = !act ? 0xFFFFFFFFu : (hi <= 0 ? 0u : (uint32_t)((hi + G - 1) / G));
-    const uint32_t klo = Gp::wave_max(k_lo), khi = min(Gp::wave_min(k_hi), Kmax - 1);
+    const int ct_full_end = ln.ct_full_end;  // first index past the whole CT blocks
+    // lean steps k in [klo, khi): every active lane absorbs a whole ciphertext block (G k + j - z in
+    // [A, ct_full_end)), so no masks, 2^128 bit selects or address recomputation. The block such a
+    // step loads for the next one may be a partial ciphertext block or lie behind the ciphertext
+    // (the lengths block's slot): the same address arithmetic fetches a partial block's bytes, and
+    // the general absorb that follows masks by rem or replaces the words. The stretch may so end at
+    // Kmax - 2, with the final absorb next (kEdge). The look-ahead reads below pay + 16 T + 20: the tag and
+    // up to 19 B behind it (a staged image: the next packet or the wave's scratch; the arena:
+    // bounds-checked loads).
+    const uint32_t klo = Gp::wave_max(ln.k_lo), khi = min(Gp::wave_min(ln.k_hi), Kmax - 1);
     for (uint32_t k = 0; k + 1 < Kmax; ++k) {
       if (k == klo && k < khi) {  // wave-uniform: the lean stretch, steps klo .. khi - 1
         // only the block address advances; i, src and rem catch up once at the end
@@ -167,6 +181,9 @@ __device__ __forceinline__ void poly_tag(const S& sp, typename S::off_t pkt, typ
         i += (int)(G * nl);
         b.src += 16 * G * nl;
         b.rem -= (int)(16 * G * nl);
+        // the block in flight lies in or just behind the ciphertext (i <= A + T): nothing of it is
+        // real exactly when it is the lengths block. b.pre stays false.
+        if (kEdge) b.lens = b.rem <= 0;
         if (k + 1 >= Kmax) break;
       }
       absorb(b, m);

@@ -17,6 +17,7 @@
 #include <stdint.h>
 
 #include "../../include/mq_aead.h"
+#include "mq_poly_sched.h"
 
 namespace mq {
 
@@ -146,6 +147,21 @@ __device__ __forceinline__ uint32_t byte_mask(int rem, int k) {  // keep bytes <
   return r >= 4 ? 0xffffffffu : (r <= 0 ? 0u : ((1u << (8 * r)) - 1u));
 }
 
+// Zero the bytes of the N words k from byte `len` on (0 <= len <= 4 N). Word m keeps all its bytes
+// when m < len / 4 and the low len % 4 of them when m == len / 4. Bit i of `upto` is set for
+// i <= len / 4; a signed 1-bit field extract spreads bit m + 1 (m < len / 4) or bit m (m <= len / 4)
+// over a word: three VALU a word.
+template <int N>
+__device__ __forceinline__ void keep_bytes(uint32_t (&k)[N], int len) {
+  const uint32_t upto = (2u << (len >> 2)) - 1u, part = (1u << (8 * (len & 3))) - 1u;
+#pragma unroll
+  for (int m = 0; m < N; ++m) {
+    const uint32_t lt = (uint32_t)__builtin_amdgcn_sbfe((int)upto, m + 1, 1);
+    const uint32_t le = (uint32_t)__builtin_amdgcn_sbfe((int)upto, m, 1);
+    k[m] = __builtin_amdgcn_bitop3_b32(k[m], lt, le & part, 0xE0);  // k & (lt | (le & part))
+  }
+}
+
 // Raw memory dwords covering N payload words at byte address `a` (for xor_words).
 template <int N, class S>
 __device__ __forceinline__ void load_raw(const S& sp, typename S::off_t a, uint32_t (&raw)[N + 1]) {
@@ -196,16 +212,7 @@ __device__ __forceinline__ void xor_words(const LdsSpace& sp, uint32_t a, const 
 #pragma unroll
   for (int m = 0; m < N; ++m) k[m] = ks[m];
   if (__builtin_amdgcn_ballot_w64(len < 4 * N) != 0) {  // wave-uniform: off the whole-block path
-    // word m keeps all its bytes when m < len / 4 and the low len % 4 of them when m == len / 4.
-    // Bit i of `upto` is set for i <= len / 4; a signed 1-bit field extract spreads bit m + 1
-    // (m < len / 4) or bit m (m <= len / 4) over a word: three VALU a word
-    const uint32_t upto = (2u << (len >> 2)) - 1u, part = (1u << (8 * (len & 3))) - 1u;
-#pragma unroll
-    for (int m = 0; m < N; ++m) {
-      const uint32_t lt = (uint32_t)__builtin_amdgcn_sbfe((int)upto, m + 1, 1);
-      const uint32_t le = (uint32_t)__builtin_amdgcn_sbfe((int)upto, m, 1);
-      k[m] = __builtin_amdgcn_bitop3_b32(k[m], lt, le & part, 0xE0);  // k & (lt | (le & part))
-    }
+    keep_bytes<N>(k, len);
   }
 #pragma unroll
   for (int m = 0; m <= N; ++m) sp.xor32(b + 4 * m, perm(m < N ? k[m] : 0u, m > 0 ? k[m - 1] : 0u, sel));
