@@ -279,6 +279,11 @@ int mq_derive_key_material(uint32_t suite, const uint8_t* secret, size_t secret_
                            mq_key_material* out);
 /* derive_next_application_secret (key_schedule.rs:114-120), label "quic ku" */
 int mq_derive_next_secret(const uint8_t* secret, size_t secret_len, uint8_t next[32]);
+/* One key update: derive_next_application_secret + derive_key_update_keys (key_schedule.rs:114-120,
+ * keys.rs:386-414). secret[32] is advanced in place; *next (which may be cur) gets cur's suite, the
+ * new key and iv, and cur's hp unchanged: the header-protection key is not updated. MQ_ERR_CRYPTO
+ * for an unknown cur->suite (secret and *next untouched), MQ_ERR_INVALID_ARG for a NULL pointer. */
+int mq_derive_key_update(uint8_t secret[32], const mq_key_material* cur, mq_key_material* next);
 
 /* ---- device key table ----------------------------------------------------------------------- */
 /* Expands every row (AES key schedules, GHASH subkey) on the host once and uploads the table. */
@@ -299,6 +304,55 @@ void mq_keytable_free(mq_keytable* kt);
 int mq_batch_derive_initial(mq_keytable* kt, uint32_t first_row, const uint8_t* dcids,
                             const uint8_t* dcid_lens, uint32_t n, mq_key_material* km_out,
                             uint8_t* status, void* stream);
+
+/* Keys of TLS traffic secrets and key updates on the GPU: the continuation of
+ * mq_batch_derive_initial for the Handshake and 1-RTT keys of a connection and for every later
+ * generation. All three calls are stream-ordered and read nothing back: enqueue them on the stream
+ * of the batches that use the rows (a batch on another stream may read a row half written). Each
+ * writes whole rows in the layout mq_keytable_create builds.
+ * Host-level returns of all three: MQ_ERR_INVALID_ARG for a NULL pointer with n > 0 (nothing
+ * launched), MQ_OK for n = 0 (nothing launched), MQ_ERR_NO_DEVICE / MQ_ERR_HIP as above.
+ *
+ * mq_batch_derive_keys: install_derived (connection/keys.rs:216-279 = derive_directional_keys,
+ * key_schedule.rs:123-151, + CryptoProvider::aead / header_protection) for n secrets of ONE suite.
+ * secrets: device, 32-byte stride. Row of secret i: row_idx[i] (device) or, when row_idx is NULL,
+ * first_row + i. km_out (device, n entries) may be NULL. status (device, n bytes): MQ_OK, or
+ * MQ_ERR_INVALID_ARG for a row index beyond the table (nothing written for that i).
+ * MQ_ERR_INVALID_ARG (nothing launched) for an unknown suite, or when row_idx is NULL and
+ * first_row + n exceeds the table. With row_idx NULL the table's host view of its rows' suites is
+ * kept exact, as by mq_keytable_update; with row_idx (and after the two calls below) the host no
+ * longer knows the rows, as after mq_batch_derive_initial: mixed batches over the table then never
+ * take the single-key ChaCha20 path. Results are the same either way. */
+int mq_batch_derive_keys(mq_keytable* kt, uint32_t suite, const uint8_t* secrets,
+                         uint32_t first_row, const uint32_t* row_idx, uint32_t n,
+                         mq_key_material* km_out, uint8_t* status, void* stream);
+/* n key updates (perform_key_update / derive_next_recv_keys, keys.rs:428-522: per entry
+ * derive_next_application_secret + derive_key_update_keys, key_schedule.rs:114-120,
+ * keys.rs:386-414). secrets (device, 32-byte stride) are advanced in place; entry i reads row
+ * src_rows[i] (its suite, its HP key) and writes row dst_rows[i] (both device; dst may equal src):
+ * the new key and iv, the AES schedule and H powers of an AES-128-GCM row, the HP key and its
+ * schedule unchanged. km_out (device, n entries) may be NULL. status[i]: MQ_ERR_INVALID_ARG for a
+ * source or destination index beyond the table; MQ_ERR_CRYPTO for an empty source row (suite 0), as
+ * derive_next_recv_keys answers Error::Crypto without installed keys; else MQ_OK. On either error
+ * the secret and the destination row stay as they were. Unspecified: two entries of one call
+ * naming the same destination row, or one entry's destination being another's source. */
+int mq_batch_key_update(mq_keytable* kt, uint8_t* secrets, const uint32_t* src_rows,
+                        const uint32_t* dst_rows, uint32_t n, mq_key_material* km_out,
+                        uint8_t* status, void* stream);
+/* The same step driven by the receive connection table, so that it never leaves the device between
+ * mq_batch_recv calls: every connection with MQ_RECV_HAS_APP and without MQ_RECV_HAS_NEXT gets its
+ * next generation (derive_next_recv_keys ahead of the peer's update, keys.rs:498-522; after
+ * confirm_peer_key_update, keys.rs:532-583, rotated it away). secrets[i] (device, 32-byte stride)
+ * is the traffic secret of connection i's newest generation derived so far (of app_row[2] with
+ * HAS_NEXT, else of app_row[1]) and is advanced. pool_first[i] (device) is the first of four
+ * consecutive key-table rows reserved for the connection's 1-RTT receive generations (the pools of
+ * different connections must not overlap). Source row: app_row[1]; destination: the lowest pool row
+ * that is not app_row[1] and, with HAS_PREV, not app_row[0]; then app_row[2] = destination and
+ * flags |= MQ_RECV_HAS_NEXT. status[i]: MQ_ERR_INVALID_ARG when pool_first[i] + 4 exceeds the
+ * table, MQ_ERR_CRYPTO when app_row[1] is beyond the table or empty (connection, secret and rows
+ * untouched in both cases); MQ_OK otherwise, also for connections that need nothing (untouched). */
+int mq_batch_recv_rekey(mq_keytable* kt, mq_conn_recv* conns, uint32_t n_conns, uint8_t* secrets,
+                        const uint32_t* pool_first, uint8_t* status, void* stream);
 
 /* ---- batch API (device pointers, stream-ordered, asynchronous) ------------------------------ */
 /* Optional length hint, OR-ed into suite_hint of mq_batch_seal / mq_batch_open and the record

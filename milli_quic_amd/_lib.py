@@ -114,7 +114,11 @@ SIGNATURES = {
     "mq_derive_initial_secrets": (ctypes.c_int, [_vp, _sz, _vp, _vp]),
     "mq_derive_key_material": (ctypes.c_int, [_u32, _vp, _sz, ctypes.POINTER(KeyMaterial)]),
     "mq_derive_next_secret": (ctypes.c_int, [_vp, _sz, _vp]),
+    "mq_derive_key_update": (ctypes.c_int, [_vp, ctypes.POINTER(KeyMaterial), ctypes.POINTER(KeyMaterial)]),
     "mq_batch_derive_initial": (ctypes.c_int, [_vp, _u32, _vp, _vp, _u32, _vp, _vp, _vp]),
+    "mq_batch_derive_keys": (ctypes.c_int, [_vp, _u32, _vp, _u32, _vp, _u32, _vp, _vp, _vp]),
+    "mq_batch_key_update": (ctypes.c_int, [_vp, _vp, _vp, _vp, _u32, _vp, _vp, _vp]),
+    "mq_batch_recv_rekey": (ctypes.c_int, [_vp, _vp, _u32, _vp, _vp, _vp, _vp]),
     "mq_batch_protect_workspace_size": (_sz, [_u32]),
     "mq_batch_protect": (ctypes.c_int, [_vp, _vp, _u32, _vp, _u64, _vp, _u64, _vp, _u32, _vp, _vp, _u32, _vp, _vp]),
     "mq_batch_recv_workspace_size": (_sz, [_u32, _u32, _u32]),

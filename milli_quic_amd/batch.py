@@ -126,6 +126,51 @@ def derive_initial(kt, first_row, dcids, dcid_lens, status, km_out=None, stream=
     _raise(rc)
 
 
+def _opt_ptr(t):
+    return ctypes.c_void_p(t.data_ptr()) if t is not None else None
+
+
+def _nbytes(t):
+    return t.numel() * t.element_size()
+
+
+def derive_keys(kt, suite, secrets, status, first_row=0, row_idx=None, km_out=None, stream=None):
+    """Batched install_derived (connection/keys.rs:216-279) on the GPU: the keys of n traffic
+    secrets of one suite (device uint8 tensor, n x 32) go into key-table rows row_idx[i] (device
+    uint32 / int32 tensor) or, without row_idx, first_row + i; km_out (n x 88 bytes) gets the key
+    material. Stream-ordered: batches that use the rows belong on the same stream."""
+    n = secrets.numel() // 32
+    if _nbytes(secrets) != 32 * n or status.numel() < n:
+        raise crypto.InvalidArgument("secrets needs 32 bytes and status 1 byte per row")
+    if row_idx is not None and _nbytes(row_idx) < 4 * n:
+        raise crypto.InvalidArgument("row_idx needs 4 bytes per row")
+    if km_out is not None and _nbytes(km_out) < 88 * n:
+        raise crypto.InvalidArgument("km_out needs 88 bytes per row")
+    rc = _lib.load().mq_batch_derive_keys(kt.handle, suite, ctypes.c_void_p(secrets.data_ptr()), first_row,
+                                          _opt_ptr(row_idx), n, _opt_ptr(km_out),
+                                          ctypes.c_void_p(status.data_ptr()), _stream_ptr(stream))
+    _raise(rc)
+
+
+def key_update(kt, secrets, src_rows, dst_rows, status, km_out=None, stream=None):
+    """Batched key update (derive_next_application_secret + derive_key_update_keys,
+    key_schedule.rs:114-120, keys.rs:386-414) on the GPU: secrets (device uint8, n x 32) advance in
+    place ("quic ku"); row dst_rows[i] gets the new key and iv of the suite of row src_rows[i] and
+    keeps its HP key (device uint32 / int32 tensors; dst may equal src). status[i]: MQ_OK,
+    MQ_ERR_INVALID_ARG (row beyond the table) or MQ_ERR_CRYPTO (empty source row)."""
+    n = secrets.numel() // 32
+    if _nbytes(secrets) != 32 * n or status.numel() < n:
+        raise crypto.InvalidArgument("secrets needs 32 bytes and status 1 byte per row")
+    if _nbytes(src_rows) < 4 * n or _nbytes(dst_rows) < 4 * n:
+        raise crypto.InvalidArgument("src_rows and dst_rows need 4 bytes per row")
+    if km_out is not None and _nbytes(km_out) < 88 * n:
+        raise crypto.InvalidArgument("km_out needs 88 bytes per row")
+    rc = _lib.load().mq_batch_key_update(kt.handle, ctypes.c_void_p(secrets.data_ptr()),
+                                         ctypes.c_void_p(src_rows.data_ptr()), ctypes.c_void_p(dst_rows.data_ptr()),
+                                         n, _opt_ptr(km_out), ctypes.c_void_p(status.data_ptr()), _stream_ptr(stream))
+    _raise(rc)
+
+
 def seal_records(kt, arena, desc, status, suite_hint, workspace=None, stream=None):
     """Seal every TLS record of `desc` (MQ_PKT_TLS_RECORD rows, tls_record.record_descs) in place:
     writes each record header and inner content type, then seals (tcp_tls/record.rs:88-113)."""

@@ -15,6 +15,19 @@
 // rows in the layout mq_keytable_create builds on the host (client keys at row 2i, server keys at
 // 2i + 1): AES round keys from the LDS T-table S-box, H^1..H^8 by the reflected GF(2^128)
 // multiply of mq_aes.h.
+//
+// Every other key of a connection comes from a 32-byte TLS traffic secret, and the same blocks
+// derive it, one lane per row again (MQRekeyConsts holds the label blocks):
+//   mq_derive_keys_kernel<SUITE>  install_derived (keys.rs:216-279): derive_directional_keys of a
+//     Handshake / 1-RTT secret of either suite -> the row build_row makes (8 compressions); the
+//     ChaCha20 instantiation has no AES schedule to expand and builds no T-table.
+//   mq_key_update_kernel          derive_next_application_secret + derive_key_update_keys
+//     (key_schedule.rs:114-120, keys.rs:386-414): "quic ku" advances the secret in place, the
+//     destination row gets the new key / iv and keeps the source row's HP key (10 compressions).
+//   mq_recv_rekey_kernel          the same step per receive connection that lacks its next
+//     generation (keys.rs:498-522), the destination row taken from the connection's 4-row pool.
+#include <stddef.h>
+
 #include "mq_aes.h"
 
 namespace mq {
@@ -113,31 +126,31 @@ __device__ __forceinline__ void aes_expand(const uint32_t (&key)[4], uint32_t rb
   }
 }
 
-// derive_directional_keys for one AES-128-GCM Initial secret -> a key-table row (+ material).
-__device__ __attribute__((noinline)) void derive_row(const MQDeriveConsts& k, const uint32_t (&secret)[8], uint32_t rb,
-                                           KeyRow* row, mq_key_material* km) {
-  const HmacPads p = hmac_pads(secret);
-  uint32_t key[8], iv[8], hp[8];
-  hmac_block(p.ist, p.ost, k.lbl[2], key);  // "quic key", 16 bytes
-  hmac_block(p.ist, p.ost, k.lbl[3], iv);   // "quic iv", 12 bytes
-  hmac_block(p.ist, p.ost, k.lbl[4], hp);   // "quic hp", 16 bytes
+// Row words both suites share, from Expand-Label outputs (big-endian SHA-256 words), as build_row
+// (mq_host.cpp) lays them out: suite, iv, the first kw key words (the rest zero).
+__device__ __forceinline__ void row_head(KeyRow* row, uint32_t suite, uint32_t kw, const uint32_t (&key)[8],
+                                         const uint32_t (&iv)[8]) {
   uint32_t* r = reinterpret_cast<uint32_t*>(row);
-  r[0] = MQ_SUITE_AES128GCM; r[1] = 0; r[2] = 0; r[3] = 0;
+  r[0] = suite; r[1] = 0; r[2] = 0; r[3] = 0;
 #pragma unroll
   for (int q = 0; q < 3; ++q) row->iv[q] = bswap32(iv[q]);
   row->pad1 = 0;
 #pragma unroll
-  for (int q = 0; q < 8; ++q) {
-    row->key[q] = q < 4 ? bswap32(key[q]) : 0u;
-    row->hp[q] = q < 4 ? bswap32(hp[q]) : 0u;
-  }
+  for (uint32_t q = 0; q < 8; ++q) row->key[q] = q < kw ? bswap32(key[q]) : 0u;
+}
+
+// What Aes128GcmProvider::header_protection precomputes: the round keys of the HP key.
+__device__ __forceinline__ void hp_schedule(const uint32_t (&hp)[8], uint32_t rb, KeyRow* row) {
   AesRk rk;
-  {
-    const uint32_t hk[4] = {hp[0], hp[1], hp[2], hp[3]};
-    aes_expand(hk, rb, rk);
+  const uint32_t hk[4] = {hp[0], hp[1], hp[2], hp[3]};
+  aes_expand(hk, rb, rk);
 #pragma unroll
-    for (int q = 0; q < 44; ++q) row->hp_rk[q] = rk.w[q];
-  }
+  for (int q = 0; q < 44; ++q) row->hp_rk[q] = rk.w[q];
+}
+
+// What Aes128GcmProvider::aead precomputes: the round keys of the AEAD key and H^1..H^8.
+__device__ __forceinline__ void aead_schedule(const uint32_t (&key)[8], uint32_t rb, KeyRow* row) {
+  AesRk rk;
   const uint32_t kk[4] = {key[0], key[1], key[2], key[3]};
   aes_expand(kk, rb, rk);
 #pragma unroll
@@ -155,15 +168,121 @@ __device__ __attribute__((noinline)) void derive_row(const MQDeriveConsts& k, co
 #pragma unroll
     for (int q = 0; q < 4; ++q) row->H[e][q] = brev(acc[q]);
   }
-  if (km) {  // mq_key_material: suite, reserved, key[32], iv[12], pad[4], hp[32] (little-endian words)
-    uint32_t* m = reinterpret_cast<uint32_t*>(km);
-    m[0] = MQ_SUITE_AES128GCM; m[1] = 0;
+}
+
+// A ChaCha20 row has no schedules: aes_rk, hp_rk and H are zero (30 x 16 B behind hp).
+__device__ __forceinline__ void zero_schedules(KeyRow* row) {
+  static_assert(offsetof(KeyRow, aes_rk) % 16 == 0 && (sizeof(KeyRow) - offsetof(KeyRow, aes_rk)) == 30 * 16,
+                "KeyRow schedules");
+  uint4* z = reinterpret_cast<uint4*>(row->aes_rk);
 #pragma unroll
-    for (int q = 0; q < 8; ++q) { m[2 + q] = row->key[q]; m[14 + q] = row->hp[q]; }
+  for (int q = 0; q < 30; ++q) z[q] = make_uint4(0, 0, 0, 0);
+}
+
+// mq_key_material of a finished row: suite, reserved, key[32], iv[12], pad[4], hp[32] (little-endian words)
+__device__ __forceinline__ void write_km(mq_key_material* km, const KeyRow* row) {
+  uint32_t* m = reinterpret_cast<uint32_t*>(km);
+  m[0] = row->suite; m[1] = 0;
 #pragma unroll
-    for (int q = 0; q < 3; ++q) m[10 + q] = row->iv[q];
-    m[13] = 0;
+  for (int q = 0; q < 8; ++q) { m[2 + q] = row->key[q]; m[14 + q] = row->hp[q]; }
+#pragma unroll
+  for (int q = 0; q < 3; ++q) m[10 + q] = row->iv[q];
+  m[13] = 0;
+}
+
+// derive_directional_keys for one AES-128-GCM Initial secret -> a key-table row (+ material).
+__device__ __attribute__((noinline)) void derive_row(const MQDeriveConsts& k, const uint32_t (&secret)[8], uint32_t rb,
+                                           KeyRow* row, mq_key_material* km) {
+  const HmacPads p = hmac_pads(secret);
+  uint32_t key[8], iv[8], hp[8];
+  hmac_block(p.ist, p.ost, k.lbl[2], key);  // "quic key", 16 bytes
+  hmac_block(p.ist, p.ost, k.lbl[3], iv);   // "quic iv", 12 bytes
+  hmac_block(p.ist, p.ost, k.lbl[4], hp);   // "quic hp", 16 bytes
+  row_head(row, MQ_SUITE_AES128GCM, 4, key, iv);
+#pragma unroll
+  for (int q = 0; q < 8; ++q) row->hp[q] = q < 4 ? bswap32(hp[q]) : 0u;
+  hp_schedule(hp, rb, row);
+  aead_schedule(key, rb, row);
+  if (km) write_km(km, row);
+}
+
+// A 32-byte secret in memory (any alignment) as big-endian SHA-256 words, and back.
+__device__ __forceinline__ void load_secret(const uint8_t* p, uint32_t (&s)[8]) {
+#pragma unroll
+  for (int q = 0; q < 8; ++q) s[q] = bswap32(reinterpret_cast<const u32_u*>(p)[q]);
+}
+__device__ __forceinline__ void store_secret(uint8_t* p, const uint32_t (&s)[8]) {
+#pragma unroll
+  for (int q = 0; q < 8; ++q) reinterpret_cast<u32_u*>(p)[q] = bswap32(s[q]);
+}
+
+// derive_directional_keys (key_schedule.rs:123-151) for one traffic secret of SUITE -> the row
+// build_row makes from the same material (+ material): 8 compressions. ChaCha20 keys are 32 bytes,
+// and so are its HP keys (max(KEY_LEN, 16), key_schedule.rs:133); its rows carry no schedules.
+template <uint32_t SUITE>
+__device__ __attribute__((noinline)) void traffic_row(const MQRekeyConsts& k, const uint32_t (&secret)[8], uint32_t rb,
+                                                      KeyRow* row, mq_key_material* km) {
+  constexpr bool kAes = SUITE == MQ_SUITE_AES128GCM;
+  constexpr uint32_t kw = kAes ? 4 : 8;
+  const HmacPads p = hmac_pads(secret);
+  uint32_t key[8], iv[8], hp[8];
+  hmac_block(p.ist, p.ost, kAes ? k.key16 : k.key32, key);
+  hmac_block(p.ist, p.ost, k.iv, iv);
+  hmac_block(p.ist, p.ost, kAes ? k.hp16 : k.hp32, hp);
+  row_head(row, SUITE, kw, key, iv);
+#pragma unroll
+  for (uint32_t q = 0; q < 8; ++q) row->hp[q] = q < kw ? bswap32(hp[q]) : 0u;
+  if constexpr (kAes) {
+    hp_schedule(hp, rb, row);
+    aead_schedule(key, rb, row);
+  } else {
+    zero_schedules(row);
   }
+  if (km) write_km(km, row);
+}
+
+// One key update (derive_next_application_secret, key_schedule.rs:114-120, then
+// derive_key_update_keys, keys.rs:386-414) of a row of `suite`: the secret at `secret` advances in
+// place, dst gets the new key and iv and keeps src's HP key (and its round keys): 10 compressions.
+// dst may be src: what the update keeps is read before anything is written.
+__device__ __attribute__((noinline)) void update_row(const MQRekeyConsts& k, uint8_t* secret, uint32_t suite, uint32_t rb,
+                                                     const KeyRow* src, KeyRow* dst, mq_key_material* km) {
+  const bool aes = suite == MQ_SUITE_AES128GCM;
+  uint32_t hp[8];
+#pragma unroll
+  for (int q = 0; q < 8; ++q) hp[q] = src->hp[q];
+  if (aes && dst != src) {
+    const uint4* f = reinterpret_cast<const uint4*>(src->hp_rk);
+    uint4* t = reinterpret_cast<uint4*>(dst->hp_rk);
+    uint4 v[11];
+#pragma unroll
+    for (int q = 0; q < 11; ++q) v[q] = f[q];
+#pragma unroll
+    for (int q = 0; q < 11; ++q) t[q] = v[q];
+  }
+  uint32_t next[8];
+  {
+    uint32_t cur[8];
+    load_secret(secret, cur);
+    const HmacPads p = hmac_pads(cur);
+    hmac_block(p.ist, p.ost, k.ku, next);
+  }
+  uint32_t key[8], iv[8];
+  {
+    const HmacPads p = hmac_pads(next);
+    uint32_t blk[16];
+#pragma unroll
+    for (int q = 0; q < 16; ++q) blk[q] = aes ? k.key16[q] : k.key32[q];
+    hmac_block(p.ist, p.ost, blk, key);
+    hmac_block(p.ist, p.ost, k.iv, iv);
+  }
+  if (!aes) zero_schedules(dst);
+  row_head(dst, suite, aes ? 4 : 8, key, iv);
+#pragma unroll
+  for (int q = 0; q < 8; ++q) dst->hp[q] = hp[q];
+  if (aes) aead_schedule(key, rb, dst);
+  store_secret(secret, next);
+  if (km) write_km(km, dst);
 }
 
 }  // namespace mq
@@ -214,5 +333,127 @@ hipError_t mq_launch_derive_initial(const MQDeriveConsts& k, const uint8_t* dcid
   if (n == 0) return hipSuccess;
   hipLaunchKernelGGL(mq_derive_initial_kernel, dim3((n + 255) / 256), dim3(256), 0, s, k, dcids, dcid_lens, n,
                      rows, km_out, status);
+  return hipGetLastError();
+}
+
+// ---- keys of a traffic secret, key updates ------------------------------------------------------
+template <uint32_t SUITE>
+__global__ __launch_bounds__(256) void mq_derive_keys_kernel(
+    MQRekeyConsts k, const uint8_t* __restrict__ secrets, uint32_t first_row, const uint32_t* __restrict__ row_idx,
+    uint32_t n, KeyRow* __restrict__ rows, uint32_t n_rows, mq_key_material* __restrict__ km_out,
+    uint8_t* __restrict__ status) {
+  uint32_t rb = 0;
+  if constexpr (SUITE == MQ_SUITE_AES128GCM) {
+    build_t0(threadIdx.x, blockDim.x);
+    __syncthreads();
+    rb = (threadIdx.x & (kTReplicas - 1)) * 4;
+  }
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const uint64_t r = row_idx ? (uint64_t)row_idx[i] : (uint64_t)first_row + i;
+  if (r >= n_rows) {
+    status[i] = MQ_ERR_INVALID_ARG;
+    return;
+  }
+  uint32_t secret[8];
+  load_secret(secrets + 32 * (size_t)i, secret);
+  traffic_row<SUITE>(k, secret, rb, rows + r, km_out ? km_out + i : nullptr);
+  status[i] = MQ_OK;
+}
+
+// The suite of a row that can be updated, else 0 (an empty row: no keys installed).
+__device__ __forceinline__ uint32_t row_suite(const KeyRow* row) {
+  const uint32_t s = row->suite;
+  return s == MQ_SUITE_AES128GCM || s == MQ_SUITE_CHACHA20 ? s : 0u;
+}
+
+extern "C" __global__ __launch_bounds__(256) void mq_key_update_kernel(
+    MQRekeyConsts k, uint8_t* secrets, const uint32_t* __restrict__ src_rows, const uint32_t* __restrict__ dst_rows,
+    uint32_t n, KeyRow* rows, uint32_t n_rows, mq_key_material* __restrict__ km_out, uint8_t* __restrict__ status) {
+  build_t0(threadIdx.x, blockDim.x);
+  __syncthreads();
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const uint32_t rb = (threadIdx.x & (kTReplicas - 1)) * 4;
+  const uint32_t src = src_rows[i], dst = dst_rows[i];
+  if (src >= n_rows || dst >= n_rows) {
+    status[i] = MQ_ERR_INVALID_ARG;
+    return;
+  }
+  const uint32_t suite = row_suite(rows + src);
+  if (!suite) {  // derive_next_recv_keys without installed keys: Error::Crypto (keys.rs:498-506)
+    status[i] = MQ_ERR_CRYPTO;
+    return;
+  }
+  update_row(k, secrets + 32 * (size_t)i, suite, rb, rows + src, rows + dst, km_out ? km_out + i : nullptr);
+  status[i] = MQ_OK;
+}
+
+extern "C" __global__ __launch_bounds__(256) void mq_recv_rekey_kernel(
+    MQRekeyConsts k, mq_conn_recv* conns, uint32_t n_conns, uint8_t* secrets, const uint32_t* __restrict__ pool_first,
+    KeyRow* rows, uint32_t n_rows, uint8_t* __restrict__ status) {
+  build_t0(threadIdx.x, blockDim.x);
+  __syncthreads();
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n_conns) return;
+  const uint32_t rb = (threadIdx.x & (kTReplicas - 1)) * 4;
+  mq_conn_recv& c = conns[i];
+  const uint32_t flags = c.flags;
+  if (!(flags & MQ_RECV_HAS_APP) || (flags & MQ_RECV_HAS_NEXT)) {  // nothing to derive ahead
+    status[i] = MQ_OK;
+    return;
+  }
+  const uint32_t pool = pool_first[i];
+  if ((uint64_t)pool + 4 > n_rows) {
+    status[i] = MQ_ERR_INVALID_ARG;
+    return;
+  }
+  const uint32_t cur = c.app_row[1], prev = c.app_row[0];
+  const uint32_t suite = cur < n_rows ? row_suite(rows + cur) : 0u;
+  if (!suite) {
+    status[i] = MQ_ERR_CRYPTO;
+    return;
+  }
+  // the lowest pool row that holds neither the current nor (while it is kept) the previous
+  // generation: two rows are taken at most, so two steps reach a free one (dst <= pool + 2)
+  uint32_t dst = pool;
+#pragma unroll
+  for (int q = 0; q < 2; ++q)
+    if (dst == cur || ((flags & MQ_RECV_HAS_PREV) && dst == prev)) ++dst;
+  update_row(k, secrets + 32 * (size_t)i, suite, rb, rows + cur, rows + dst, nullptr);
+  c.app_row[2] = dst;
+  c.flags = (uint8_t)(flags | MQ_RECV_HAS_NEXT);
+  status[i] = MQ_OK;
+}
+
+hipError_t mq_launch_derive_keys(const MQRekeyConsts& k, uint32_t suite, const uint8_t* secrets, uint32_t first_row,
+                                 const uint32_t* row_idx, uint32_t n, KeyRow* rows, uint32_t n_rows,
+                                 mq_key_material* km_out, uint8_t* status, hipStream_t s) {
+  if (n == 0) return hipSuccess;
+  const dim3 grid((n + 255) / 256), block(256);
+  if (suite == MQ_SUITE_AES128GCM)
+    hipLaunchKernelGGL(mq_derive_keys_kernel<MQ_SUITE_AES128GCM>, grid, block, 0, s, k, secrets, first_row, row_idx, n,
+                       rows, n_rows, km_out, status);
+  else
+    hipLaunchKernelGGL(mq_derive_keys_kernel<MQ_SUITE_CHACHA20>, grid, block, 0, s, k, secrets, first_row, row_idx, n,
+                       rows, n_rows, km_out, status);
+  return hipGetLastError();
+}
+
+hipError_t mq_launch_key_update(const MQRekeyConsts& k, uint8_t* secrets, const uint32_t* src_rows,
+                                const uint32_t* dst_rows, uint32_t n, KeyRow* rows, uint32_t n_rows,
+                                mq_key_material* km_out, uint8_t* status, hipStream_t s) {
+  if (n == 0) return hipSuccess;
+  hipLaunchKernelGGL(mq_key_update_kernel, dim3((n + 255) / 256), dim3(256), 0, s, k, secrets, src_rows, dst_rows, n,
+                     rows, n_rows, km_out, status);
+  return hipGetLastError();
+}
+
+hipError_t mq_launch_recv_rekey(const MQRekeyConsts& k, mq_conn_recv* conns, uint32_t n_conns, uint8_t* secrets,
+                                const uint32_t* pool_first, KeyRow* rows, uint32_t n_rows, uint8_t* status,
+                                hipStream_t s) {
+  if (n_conns == 0) return hipSuccess;
+  hipLaunchKernelGGL(mq_recv_rekey_kernel, dim3((n_conns + 255) / 256), dim3(256), 0, s, k, conns, n_conns, secrets,
+                     pool_first, rows, n_rows, status);
   return hipGetLastError();
 }

@@ -58,6 +58,13 @@ struct MQDeriveConsts {
   uint32_t lbl[5][16];
 };
 
+// Constants of the batched traffic-secret derivation and key update (mq_derive.hip): the same
+// padded label blocks for "quic key" (16 and 32), "quic iv" (12), "quic hp" (16 and 32) and
+// "quic ku" (32). A 32-byte output is still the one HKDF block T(1).
+struct MQRekeyConsts {
+  uint32_t key16[16], key32[16], iv[16], hp16[16], hp32[16], ku[16];
+};
+
 // The AEAD passes of the datagram receive composite (mq_recv.hip), run by mq_host.cpp's batch
 // driver: primary descriptors / statuses, retry (previous-generation keys) descriptors / statuses.
 struct MQRecvPass {

@@ -113,6 +113,15 @@ uint32_t mq_partition_list_cap(uint32_t n);
 hipError_t mq_launch_derive_initial(const mq::MQDeriveConsts& k, const uint8_t* dcids, const uint8_t* dcid_lens,
                                     uint32_t n, KeyRow* rows, mq_key_material* km_out, uint8_t* status,
                                     hipStream_t s);
+hipError_t mq_launch_derive_keys(const mq::MQRekeyConsts& k, uint32_t suite, const uint8_t* secrets, uint32_t first_row,
+                                 const uint32_t* row_idx, uint32_t n, KeyRow* rows, uint32_t n_rows,
+                                 mq_key_material* km_out, uint8_t* status, hipStream_t s);
+hipError_t mq_launch_key_update(const mq::MQRekeyConsts& k, uint8_t* secrets, const uint32_t* src_rows,
+                                const uint32_t* dst_rows, uint32_t n, KeyRow* rows, uint32_t n_rows,
+                                mq_key_material* km_out, uint8_t* status, hipStream_t s);
+hipError_t mq_launch_recv_rekey(const mq::MQRekeyConsts& k, mq_conn_recv* conns, uint32_t n_conns, uint8_t* secrets,
+                                const uint32_t* pool_first, KeyRow* rows, uint32_t n_rows, uint8_t* status,
+                                hipStream_t s);
 hipError_t mq_launch_build(const KeyRow* kt, uint32_t n_rows, const mq_conn_send* conns, uint32_t n_conns,
                            const uint8_t* frames, uint64_t frames_len, uint8_t* out, uint64_t out_len,
                            const mq_send_req* req, uint32_t n, mq_pkt_desc* desc, uint8_t* bstatus,
@@ -897,6 +906,24 @@ int mq_derive_next_secret(const uint8_t* secret, size_t secret_len, uint8_t next
   return mq_hkdf_expand_label(secret, secret_len, (const uint8_t*)"quic ku", 7, nullptr, 0, next, 32);
 }
 
+int mq_derive_key_update(uint8_t secret[32], const mq_key_material* cur, mq_key_material* next) {
+  if (!secret || !cur || !next) return MQ_ERR_INVALID_ARG;
+  const size_t klen = suite_key_len(cur->suite);
+  if (!klen) return MQ_ERR_CRYPTO;
+  uint8_t ns[32];
+  mq_key_material km;
+  std::memset(&km, 0, sizeof km);
+  km.suite = cur->suite;
+  int rc = mq_derive_next_secret(secret, 32, ns);
+  if (!rc) rc = mq_hkdf_expand_label(ns, 32, (const uint8_t*)"quic key", 8, nullptr, 0, km.key, klen);
+  if (!rc) rc = mq_hkdf_expand_label(ns, 32, (const uint8_t*)"quic iv", 7, nullptr, 0, km.iv, 12);
+  if (rc) return rc;
+  std::memcpy(km.hp, cur->hp, sizeof km.hp);  // the HP key is not updated (keys.rs:386-414)
+  std::memcpy(secret, ns, 32);
+  *next = km;  // next may be cur
+  return MQ_OK;
+}
+
 int mq_keytable_create(const mq_key_material* rows, uint32_t n_rows, mq_keytable** out) {
   if (!out || (!rows && n_rows)) return MQ_ERR_INVALID_ARG;
   *out = nullptr;
@@ -1105,6 +1132,20 @@ const mq::MQDeriveConsts& derive_consts() {
   });
   return k;
 }
+
+const mq::MQRekeyConsts& rekey_consts() {
+  static mq::MQRekeyConsts k;
+  static std::once_flag once;
+  std::call_once(once, [] {
+    label_block("quic key", 16, k.key16);
+    label_block("quic key", 32, k.key32);
+    label_block("quic iv", 12, k.iv);
+    label_block("quic hp", 16, k.hp16);
+    label_block("quic hp", 32, k.hp32);
+    label_block("quic ku", 32, k.ku);
+  });
+  return k;
+}
 }  // namespace
 
 extern "C" {
@@ -1120,6 +1161,51 @@ int mq_batch_derive_initial(mq_keytable* kt, uint32_t first_row, const uint8_t* 
   kt->derived = kt->derived || n > 0;
   return mq_launch_derive_initial(derive_consts(), dcids, dcid_lens, n, kt->dev + first_row, km_out, status,
                                   (hipStream_t)stream) == hipSuccess
+             ? MQ_OK
+             : MQ_ERR_HIP;
+}
+
+// ---- keys of traffic secrets and key updates (keys.rs:216-279, :386-583) ----------------------
+int mq_batch_derive_keys(mq_keytable* kt, uint32_t suite, const uint8_t* secrets, uint32_t first_row,
+                         const uint32_t* row_idx, uint32_t n, mq_key_material* km_out, uint8_t* status, void* stream) {
+  if (!kt || (n && (!secrets || !status)) || !suite_key_len(suite)) return MQ_ERR_INVALID_ARG;
+  if (!row_idx && (uint64_t)first_row + n > kt->rows) return MQ_ERR_INVALID_ARG;
+  DeviceGuard g(kt->device);
+  if (!g.ok()) return MQ_ERR_NO_DEVICE;
+  if (n == 0) return MQ_OK;
+  if (mq_launch_derive_keys(rekey_consts(), suite, secrets, first_row, row_idx, n, kt->dev, kt->rows, km_out, status,
+                            (hipStream_t)stream) != hipSuccess)
+    return MQ_ERR_HIP;
+  // consecutive rows: every written row's suite is known here, so the host view stays exact (a
+  // table with one ChaCha20 row keeps its single-key list path); scattered rows are known to the
+  // device only
+  if (row_idx) kt->derived = true;
+  else kt_mirror(kt, first_row, n, [&](uint32_t) { return (uint8_t)suite; });
+  return MQ_OK;
+}
+
+int mq_batch_key_update(mq_keytable* kt, uint8_t* secrets, const uint32_t* src_rows, const uint32_t* dst_rows,
+                        uint32_t n, mq_key_material* km_out, uint8_t* status, void* stream) {
+  if (!kt || (n && (!secrets || !src_rows || !dst_rows || !status))) return MQ_ERR_INVALID_ARG;
+  DeviceGuard g(kt->device);
+  if (!g.ok()) return MQ_ERR_NO_DEVICE;
+  if (n == 0) return MQ_OK;
+  kt->derived = true;  // the rows and their suites are known to the device only
+  return mq_launch_key_update(rekey_consts(), secrets, src_rows, dst_rows, n, kt->dev, kt->rows, km_out, status,
+                              (hipStream_t)stream) == hipSuccess
+             ? MQ_OK
+             : MQ_ERR_HIP;
+}
+
+int mq_batch_recv_rekey(mq_keytable* kt, mq_conn_recv* conns, uint32_t n_conns, uint8_t* secrets,
+                        const uint32_t* pool_first, uint8_t* status, void* stream) {
+  if (!kt || (n_conns && (!conns || !secrets || !pool_first || !status))) return MQ_ERR_INVALID_ARG;
+  DeviceGuard g(kt->device);
+  if (!g.ok()) return MQ_ERR_NO_DEVICE;
+  if (n_conns == 0) return MQ_OK;
+  kt->derived = true;  // as above
+  return mq_launch_recv_rekey(rekey_consts(), conns, n_conns, secrets, pool_first, kt->dev, kt->rows, status,
+                              (hipStream_t)stream) == hipSuccess
              ? MQ_OK
              : MQ_ERR_HIP;
 }

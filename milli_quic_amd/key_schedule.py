@@ -49,6 +49,19 @@ def derive_next_application_secret(current_secret):
     return bytes(out)
 
 
+def derive_key_update(secret, cur_km):
+    """One key update (derive_next_application_secret + derive_key_update_keys,
+    key_schedule.rs:114-120, keys.rs:386-414) -> (next_secret, next_km): the new key and iv, the
+    suite and HP key of cur_km."""
+    secret = bytes(secret)
+    if len(secret) != 32:
+        raise CryptoError("a traffic secret has 32 bytes")
+    s = (ctypes.c_uint8 * 32).from_buffer_copy(secret)
+    km = _lib.KeyMaterial()
+    _raise(_lib.load().mq_derive_key_update(s, ctypes.byref(cur_km), ctypes.byref(km)))
+    return bytes(s), km
+
+
 def key_material(suite, secret):
     """derive_directional_keys' key/iv/hp (key_schedule.rs:123-151) as an mq_key_material row."""
     km = _lib.KeyMaterial()

@@ -47,3 +47,21 @@ def recv(kt, conns, arena, dgrams, pkts, n_pkts, workspace, stream=None):
         ctypes.c_void_p(dgrams.data_ptr()), n_dgrams, ctypes.c_void_p(pkts.data_ptr()), max_pkts,
         ctypes.c_void_p(n_pkts.data_ptr()), ctypes.c_void_p(workspace.data_ptr()), _stream_ptr(stream))
     _raise(rc)
+
+
+def rekey(kt, conns, secrets, pool_first, status, stream=None):
+    """mq_batch_recv_rekey: every connection with HAS_APP and without HAS_NEXT gets its next 1-RTT
+    generation derived on the device (derive_next_recv_keys, keys.rs:498-522), so the connection
+    table stays device-resident across key updates. secrets (device uint8, n_conns x 32: each
+    connection's newest traffic secret) advance in place; the new row is the lowest free one of the
+    four rows from pool_first[i] (device uint32 / int32); conns gets app_row[2] and HAS_NEXT.
+    status[i]: MQ_OK, MQ_ERR_INVALID_ARG (pool beyond the table) or MQ_ERR_CRYPTO (no current keys)."""
+    n_conns = conns.numel() // CONN_DTYPE.itemsize
+    if secrets.numel() * secrets.element_size() < 32 * n_conns or status.numel() < n_conns:
+        raise InvalidArgument("secrets needs 32 bytes and status 1 byte per connection")
+    if pool_first.numel() * pool_first.element_size() < 4 * n_conns:
+        raise InvalidArgument("pool_first needs 4 bytes per connection")
+    rc = _lib.load().mq_batch_recv_rekey(
+        kt.handle, ctypes.c_void_p(conns.data_ptr()), n_conns, ctypes.c_void_p(secrets.data_ptr()),
+        ctypes.c_void_p(pool_first.data_ptr()), ctypes.c_void_p(status.data_ptr()), _stream_ptr(stream))
+    _raise(rc)

@@ -9,7 +9,10 @@ stream; median of `reps`). Prints one JSON object; the round's copy lives in pro
            (AES-128-GCM)
   hp_mask  mq_batch_hp_mask (SURVEY §8d "mask-only timing"): 2^20 16-B samples -> 5-B masks,
            AES-128 (config C keys) and ChaCha20 (config B keys)
-Usage: python tools/bench_aux.py [reps]
+  rekey    mq_batch_derive_keys / mq_batch_key_update: 2^20 traffic secrets -> rows, per suite; a
+           4096-row sample of the key material byte-checked against the host functions; the host
+           path (HKDF per row + one mq_keytable_update) over 2^14 of the same rows
+Usage: python tools/bench_aux.py [reps] | rekey [reps] | recv reps conns...
 """
 import json
 import os
@@ -164,7 +167,69 @@ def bench_hp_mask(reps, suite, n=1 << 20):
     return {"samples": n, "ms": round(ms, 4), "masks_per_s": round(n / ms * 1e3)}
 
 
+def bench_rekey(reps, suite, n=1 << 20, n_host=1 << 14, k=4096):
+    """derive_keys and key_update (dst == src) over n rows of one suite; a k-row sample of km_out
+    byte-checked against the host functions; the host path for the first n_host of the same rows:
+    mq_derive_key_material (mq_derive_key_update) per row through ctypes plus one mq_keytable_update."""
+    import ctypes
+    import time
+    from milli_quic_amd import key_schedule
+    lib = _lib.load()
+    KM = ctypes.sizeof(_lib.KeyMaterial)
+    kt = KeyTable([_lib.KeyMaterial() for _ in range(n)])
+    sec = workload.splitmix_bytes(32 * n, seed=13).reshape(n, 32)
+    s_d, st = t(sec), torch.zeros(n, dtype=torch.uint8, device=DEV)
+    km = torch.zeros(KM * n, dtype=torch.uint8, device=DEV)
+    rows = torch.arange(n, dtype=torch.int32, device=DEV)
+    ms_d = timed(lambda: batch.derive_keys(kt, suite, s_d, st, km_out=km), reps)
+    assert int((st != 0).sum()) == 0
+    km0 = km.cpu().numpy().reshape(n, KM)
+    pick = np.random.default_rng(12).choice(n, size=k, replace=False)
+    host0 = {int(i): key_schedule.key_material(suite, sec[i].tobytes()) for i in pick}
+    assert all(km0[i].tobytes() == bytes(host0[i]) for i in host0)
+    s_u = s_d.clone()
+    batch.key_update(kt, s_u, rows, rows, st, km_out=km)  # generation 1 of every row, then the timed ones
+    torch.cuda.synchronize()
+    assert int((st != 0).sum()) == 0
+    km1, s1 = km.cpu().numpy().reshape(n, KM), s_u.cpu().numpy().reshape(n, 32)
+    for i in host0:
+        nxt, want = key_schedule.derive_key_update(sec[i].tobytes(), host0[i])
+        assert s1[i].tobytes() == nxt and km1[i].tobytes() == bytes(want)
+    ms_u = timed(lambda: batch.key_update(kt, s_u, rows, rows, st, km_out=km), reps)
+    assert int((st != 0).sum()) == 0
+    # host path: HKDF per row on one thread, then the synchronous row upload
+    arr = (_lib.KeyMaterial * n_host)()
+    blobs = [sec[i].tobytes() for i in range(n_host)]
+    t0 = time.perf_counter()
+    for i in range(n_host):
+        lib.mq_derive_key_material(suite, blobs[i], 32, ctypes.byref(arr[i]))
+    assert lib.mq_keytable_update(kt.handle, 0, arr, n_host) == 0
+    h_d = time.perf_counter() - t0
+    bufs = [(ctypes.c_uint8 * 32).from_buffer_copy(b) for b in blobs]
+    t0 = time.perf_counter()
+    for i in range(n_host):
+        lib.mq_derive_key_update(bufs[i], ctypes.byref(arr[i]), ctypes.byref(arr[i]))
+    assert lib.mq_keytable_update(kt.handle, 0, arr, n_host) == 0
+    h_u = time.perf_counter() - t0
+    assert bytes(arr[int(pick[0]) % n_host]) == km1[int(pick[0]) % n_host].tobytes()
+    out = {"rows": n, "sample_checked": k, "host_rows": n_host,
+           "derive_keys_ms": round(ms_d, 4), "derive_keys_rows_per_s": round(n / ms_d * 1e3),
+           "key_update_ms": round(ms_u, 4), "key_update_rows_per_s": round(n / ms_u * 1e3),
+           "host_derive_rows_per_s": round(n_host / h_d), "host_key_update_rows_per_s": round(n_host / h_u)}
+    out["derive_keys_vs_host"] = round(out["derive_keys_rows_per_s"] / out["host_derive_rows_per_s"], 1)
+    out["key_update_vs_host"] = round(out["key_update_rows_per_s"] / out["host_key_update_rows_per_s"], 1)
+    return out
+
+
 def main():
+    if len(sys.argv) > 1 and sys.argv[1] == "rekey":  # key derivation / update runs only: rekey [REPS]
+        assert _lib.load().mq_device_init(0) == 0
+        reps = int(sys.argv[2]) if len(sys.argv) > 2 else 5
+        res = {"device": torch.cuda.get_device_name(0),
+               "rekey_aes": bench_rekey(reps, _lib.MQ_SUITE_AES128GCM),
+               "rekey_chacha": bench_rekey(reps, _lib.MQ_SUITE_CHACHA20)}
+        print(json.dumps(res), flush=True)
+        return
     if len(sys.argv) > 1 and sys.argv[1] == "recv":  # receive runs only: recv REPS CONNS...
         assert _lib.load().mq_device_init(0) == 0
         reps = int(sys.argv[2])
@@ -183,6 +248,8 @@ def main():
     res["records_16k"] = bench_records(reps, 1 << 16, 16384 + 5 + 17)
     res["hp_mask_aes"] = bench_hp_mask(reps, _lib.MQ_SUITE_AES128GCM)
     res["hp_mask_chacha"] = bench_hp_mask(reps, _lib.MQ_SUITE_CHACHA20)
+    res["rekey_aes"] = bench_rekey(reps, _lib.MQ_SUITE_AES128GCM)
+    res["rekey_chacha"] = bench_rekey(reps, _lib.MQ_SUITE_CHACHA20)
     print(json.dumps(res), flush=True)
 
 
