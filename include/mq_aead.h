@@ -151,7 +151,8 @@ typedef struct mq_send_req {        /* one packet to build and protect          
 typedef struct mq_dgram {           /* one received UDP datagram, in arrival order              */
   uint64_t offset;                  /* in the arena                                             */
   uint32_t len;
-  uint32_t conn;                    /* row of the connection table (the caller's DCID lookup)    */
+  uint32_t conn;                    /* row of the connection table (mq_batch_route fills it in,
+                                       or the caller's own DCID lookup)                          */
 } mq_dgram;                         /* 16 bytes */
 
 typedef struct mq_conn_recv {       /* receive-side connection state, updated in place           */
@@ -433,6 +434,119 @@ size_t mq_batch_recv_workspace_size(uint32_t n_dgrams, uint32_t max_pkts, uint32
 int mq_batch_recv(const mq_keytable* kt, mq_conn_recv* conns, uint32_t n_conns, uint8_t* arena,
                   uint64_t arena_len, const mq_dgram* dgrams, uint32_t n_dgrams, mq_recv_pkt* pkts,
                   uint32_t max_pkts, uint32_t* n_pkts, void* workspace, void* stream);
+
+/* ---- datagram routing: device-resident connection-ID table and admission ------------------------
+ * The step in front of mq_batch_recv: filling mq_dgram.conn from each datagram's Destination
+ * Connection ID, and admitting the connections that first Initial packets open, so that the socket
+ * buffer is the input of the receive side. The reference has no multi-connection
+ * router (its Connection is one connection, the application routes); per datagram the semantics are
+ * pinned to
+ *   decode_dcid                  src/packet/decode_dcid.rs:9-37 (the CID of a long / short header;
+ *                                None for a datagram too short to hold it),
+ *   the first-Initial rule       src/connection/recv.rs:275-278 (a server's connection starts with
+ *                                the client's first Initial, whose DCID keys the Initial secrets),
+ *   RFC 9000 §5.2 (matching datagrams to connections by DCID), §14.1 (a server discards Initials in
+ *   datagrams below 1200 bytes), §17.2 (long header: version, DCID length <= 20; version 0 is
+ *   Version Negotiation).
+ *
+ * A table maps CIDs of 0..20 bytes (the empty CID is a valid key) to connection rows by exact
+ * comparison of (length, bytes). It lives on the device it was created on, like a key table, and all
+ * calls on it are stream-ordered: enqueue them on ONE stream (a call on another stream may see a
+ * table half written). `capacity` is the largest number of live entries; the table holds a power of
+ * two >= 2 x capacity slots of 32 bytes, probed linearly from a SipHash-1-3 of the CID keyed with
+ * `seed` (Initial DCIDs are chosen by the peer; pick the seed at random per process).
+ * Host-level returns of every call below: MQ_ERR_INVALID_ARG for a NULL pointer with n > 0 and for
+ * the argument errors named per call — checked first, nothing launched —, MQ_OK for n = 0,
+ * MQ_ERR_NO_DEVICE / MQ_ERR_HIP as elsewhere. All pointers are device memory except `seed`, the
+ * mq_route_admit struct itself and the outputs of mq_cid_table_stats. */
+typedef struct mq_cid_table mq_cid_table;
+#define MQ_CONN_NONE 0xFFFFFFFFu    /* no connection: mq_batch_recv skips datagrams with conn >= n_conns */
+
+/* per-datagram route status (also the per-entry status of insert / remove, which add MQ_OK) */
+#define MQ_ROUTE_HIT       0  /* CID in the table: conn written                                       */
+#define MQ_ROUTE_NEW       1  /* admitted by this call (every datagram of the new connection): conn
+                                 written                                                              */
+#define MQ_ROUTE_UNKNOWN   2  /* not in the table and not admissible: conn = MQ_CONN_NONE             */
+#define MQ_ROUTE_MALFORMED 3  /* decode_dcid -> None, a long-header DCID length over 20, or a datagram
+                                 outside the arena                                                    */
+#define MQ_ROUTE_FULL      4  /* admissible, but max_new or the table's capacity is used up           */
+#define MQ_ROUTE_DEFERRED  5  /* lost a hash collision against another NEW CID of this batch (all 64
+                                 bits of the slot word equal): untouched, resubmit                    */
+
+int mq_cid_table_create(uint32_t capacity, const uint8_t seed[16], mq_cid_table** out);
+void mq_cid_table_free(mq_cid_table* t);
+/* n entries: cids (20-byte stride, bytes from lens[i] on are ignored), lens, conn. status[i]: MQ_OK
+ * for a new entry; MQ_ROUTE_HIT if the CID was in the table before the call (the entry stays as it
+ * was); MQ_ROUTE_FULL at capacity; MQ_ROUTE_MALFORMED for a length over 20. Two entries of one call
+ * with the same CID both take a slot (which conn a lookup then answers is unspecified); one remove
+ * of that CID frees both. Which entries of a call that overruns the capacity get MQ_ROUTE_FULL is
+ * unspecified (their number is not). */
+int mq_cid_table_insert(mq_cid_table* t, const uint8_t* cids, const uint8_t* lens, const uint32_t* conn,
+                        uint32_t n, uint8_t* status, void* stream);
+/* status[i]: MQ_OK (every lookup of the CID misses from now on, the slot counts as free at once) or
+ * MQ_ROUTE_UNKNOWN. Of two entries of one call with the same CID, at least one gets MQ_OK. */
+int mq_cid_table_remove(mq_cid_table* t, const uint8_t* cids, const uint8_t* lens, uint32_t n,
+                        uint8_t* status, void* stream);
+/* Rehashes the live entries into a second buffer and drops the tombstones that removals leave
+ * (they lengthen probe chains until then): call it when mq_cid_table_stats shows many. A table
+ * survives insert / remove churn of any length this way. */
+int mq_cid_table_compact(mq_cid_table* t, void* stream);
+/* Waits for the stream, then reports live entries, tombstones and the slot count (NULL = not wanted). */
+int mq_cid_table_stats(const mq_cid_table* t, void* stream, uint32_t* live, uint32_t* tombstones,
+                       uint32_t* slots);
+/* Diagnostic, empty table only (else MQ_ERR_INVALID_ARG; synchronises the device): keep the low
+ * `bits` (1..64) of the hash, so that tests can force collisions. Results never depend on it, except
+ * that MQ_ROUTE_DEFERRED becomes likely. */
+int mq_debug_cid_table_hash_bits(mq_cid_table* t, uint32_t bits);
+
+typedef struct mq_route_admit {     /* NULL = look up only                                       */
+  mq_conn_recv* conns;              /* rows [conn_base, conn_base + max_new) are initialised for   */
+  uint32_t n_conns;                 /* admitted connections; the others are not touched            */
+  uint32_t conn_base, max_new;
+  uint32_t row_first;               /* key-table row of new connection k's client Initial keys (its
+                                       receive keys) = row_first + 2k, of its server Initial keys
+                                       (mq_conn_send.key_row[0]) = row_first + 2k + 1: what
+                                       mq_batch_derive_initial(first_row = row_first) writes         */
+  uint32_t min_initial_len;         /* RFC 9000 §14.1: 1200; 0 = no check                          */
+  uint8_t*  new_dcids;              /* 20-byte stride, max_new entries                              */
+  uint8_t*  new_dcid_lens;          /* max_new bytes                                                */
+  uint32_t* n_new;                  /* one word                                                     */
+} mq_route_admit;                   /* 56 bytes */
+
+/* Per datagram i, in this order:
+ *  1. offset + len > arena_len: MQ_ROUTE_MALFORMED.
+ *  2. The CID as decode_dcid extracts it. Empty datagram: MALFORMED. Long header (byte 0 & 0x80):
+ *     len < 6, len < 6 + L for the DCID length L = byte 5, or L > 20 (ours: no key is longer, §17.2):
+ *     MALFORMED; else bytes 6..6+L. Short header: len < 1 + short_dcid_len: MALFORMED; else bytes
+ *     1..1+short_dcid_len (0: the empty CID). No byte at or past offset + len is loaded.
+ *  3. Lookup in the table as it was when the call started. Found: MQ_ROUTE_HIT, conn = the entry's.
+ *  4. A miss is admissible if admit != NULL, the header is long with (byte 0 & 0x30) == 0 (Initial),
+ *     the version (bytes 1..4) is not 0 and len >= min_initial_len. Any other miss: MQ_ROUTE_UNKNOWN.
+ *  5. Admissible misses are grouped by CID; the groups are ranked by their lowest datagram index.
+ *     Group k is admitted if k < min(max_new, capacity - live entries at the start of the call):
+ *     all its datagrams get MQ_ROUTE_NEW and conn = conn_base + k; new_dcids[k], new_dcid_lens[k]
+ *     and the table entry are written; conns[conn_base + k] is zeroed, then initial_row =
+ *     row_first + 2k, flags = MQ_RECV_HAS_INITIAL, dcid_len = short_dcid_len. The other groups get
+ *     MQ_ROUTE_FULL.
+ *  6. *n_new = the number of admitted groups; new_dcid_lens[k] = 0xFF for n_new <= k < max_new
+ *     (new_dcids beyond n_new is left as it was). So mq_batch_derive_initial(kt, row_first,
+ *     new_dcids, new_dcid_lens, max_new, ..) and then mq_batch_recv can follow on the same stream
+ *     with nothing read back: a length over 20 only gives its two rows suite 0.
+ * dgrams[i].conn is overwritten for every datagram (MQ_CONN_NONE unless HIT or NEW); nothing else
+ * of dgrams and nothing of the arena is written. The result is a function of the inputs alone: the
+ * same call on the same table contents gives the same statuses, conn values and new_* arrays.
+ * Groups whose slot words collide (same hash bits and length, different bytes) are told apart: the
+ * one with the lowest datagram index is ranked, the datagrams of the others get MQ_ROUTE_DEFERRED and
+ * take no part in the ranking — resubmit them in a later call.
+ * MQ_ERR_INVALID_ARG also for short_dcid_len > 20 and conn_base + max_new > n_conns. `workspace`
+ * (mq_batch_route_workspace_size(n_dgrams) bytes, contents need not be initialised) is needed with
+ * admit only. With n_dgrams = 0 and admit, *n_new = 0 and the 0xFF lengths are still written.
+ * At most 2^30 datagrams per call; dgrams and workspace must be 16-byte aligned (else
+ * MQ_ERR_INVALID_ARG). */
+size_t mq_batch_route_workspace_size(uint32_t n_dgrams);
+int mq_batch_route(mq_cid_table* t, const uint8_t* arena, uint64_t arena_len, mq_dgram* dgrams,
+                   uint32_t n_dgrams, uint32_t short_dcid_len, const mq_route_admit* admit,
+                   uint8_t* status, void* workspace, void* stream);
 
 /* Batched HeaderProtection::mask: masks[i*5..] = mask(key_table[key_ids[i]].hp, samples[i*16..]).
  * An entry whose key id is out of range or whose row holds no valid suite gets an all-zero mask

@@ -11,8 +11,11 @@ from . import _lib  # noqa: F401
 from .crypto import (Aes128GcmAead, Aes128GcmProvider, AesHeaderProtection, BufferTooSmall,  # noqa: F401
                      ChaCha20Poly1305Aead, ChaCha20Provider, ChaChaHeaderProtection, CryptoError,
                      DirectionalKeys, Error, HkdfSha256, InvalidArgument, ProtocolViolation, nonce)
+from . import route  # noqa: F401,E402
+from .route import Admit, CidTable  # noqa: F401,E402
 
 __all__ = [
+    "Admit", "CidTable", "route",
     "Aes128GcmAead", "Aes128GcmProvider", "AesHeaderProtection", "BufferTooSmall", "ChaCha20Poly1305Aead",
     "ChaCha20Provider", "ChaChaHeaderProtection", "CryptoError", "DirectionalKeys", "Error", "HkdfSha256",
     "InvalidArgument", "ProtocolViolation", "nonce",

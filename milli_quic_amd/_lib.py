@@ -46,6 +46,10 @@ MQ_RECV_MAX_PACKET = 2048
 MQ_LEVEL_INITIAL, MQ_LEVEL_HANDSHAKE, MQ_LEVEL_APPLICATION = 0, 1, 2
 MQ_SEND_PAD_TO_MIN = 0x01
 
+MQ_CONN_NONE = 0xFFFFFFFF
+(MQ_ROUTE_HIT, MQ_ROUTE_NEW, MQ_ROUTE_UNKNOWN, MQ_ROUTE_MALFORMED, MQ_ROUTE_FULL,
+ MQ_ROUTE_DEFERRED) = range(6)
+
 
 class KeyMaterial(ctypes.Structure):
     """mq_key_material: what CryptoProvider::aead + ::header_protection consume."""
@@ -75,8 +79,25 @@ class PktDesc(ctypes.Structure):
     ]
 
 
+class RouteAdmit(ctypes.Structure):
+    """mq_route_admit: where mq_batch_route puts the connections it admits (device pointers)."""
+
+    _fields_ = [
+        ("conns", ctypes.c_void_p),
+        ("n_conns", ctypes.c_uint32),
+        ("conn_base", ctypes.c_uint32),
+        ("max_new", ctypes.c_uint32),
+        ("row_first", ctypes.c_uint32),
+        ("min_initial_len", ctypes.c_uint32),
+        ("new_dcids", ctypes.c_void_p),
+        ("new_dcid_lens", ctypes.c_void_p),
+        ("n_new", ctypes.c_void_p),
+    ]
+
+
 assert ctypes.sizeof(KeyMaterial) == 88
 assert ctypes.sizeof(PktDesc) == 32
+assert ctypes.sizeof(RouteAdmit) == 56
 
 _u8p = ctypes.POINTER(ctypes.c_uint8)
 _vp = ctypes.c_void_p
@@ -123,6 +144,16 @@ SIGNATURES = {
     "mq_batch_protect": (ctypes.c_int, [_vp, _vp, _u32, _vp, _u64, _vp, _u64, _vp, _u32, _vp, _vp, _u32, _vp, _vp]),
     "mq_batch_recv_workspace_size": (_sz, [_u32, _u32, _u32]),
     "mq_batch_recv": (ctypes.c_int, [_vp, _vp, _u32, _vp, _u64, _vp, _u32, _vp, _u32, _vp, _vp, _vp]),
+    "mq_cid_table_create": (ctypes.c_int, [_u32, _vp, ctypes.POINTER(_vp)]),
+    "mq_cid_table_free": (None, [_vp]),
+    "mq_cid_table_insert": (ctypes.c_int, [_vp, _vp, _vp, _vp, _u32, _vp, _vp]),
+    "mq_cid_table_remove": (ctypes.c_int, [_vp, _vp, _vp, _u32, _vp, _vp]),
+    "mq_cid_table_compact": (ctypes.c_int, [_vp, _vp]),
+    "mq_cid_table_stats": (ctypes.c_int, [_vp, _vp, ctypes.POINTER(_u32), ctypes.POINTER(_u32),
+                                          ctypes.POINTER(_u32)]),
+    "mq_debug_cid_table_hash_bits": (ctypes.c_int, [_vp, _u32]),
+    "mq_batch_route_workspace_size": (_sz, [_u32]),
+    "mq_batch_route": (ctypes.c_int, [_vp, _vp, _u64, _vp, _u32, _u32, ctypes.POINTER(RouteAdmit), _vp, _vp, _vp]),
     "mq_keytable_create": (ctypes.c_int, [ctypes.POINTER(KeyMaterial), _u32, ctypes.POINTER(_vp)]),
     "mq_keytable_update": (ctypes.c_int, [_vp, _u32, ctypes.POINTER(KeyMaterial), _u32]),
     "mq_keytable_rows": (_u32, [_vp]),

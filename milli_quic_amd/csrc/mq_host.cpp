@@ -13,11 +13,13 @@
 #include <cstdlib>
 #include <cstring>
 #include <mutex>
+#include <utility>
 #include <vector>
 
 #include "mq_device.h"
 #include "mq_opts.h"
 #include "mq_resident.h"
+#include "mq_route.h"
 #include "mq_runtime.h"
 
 using mq::KeyRow;
@@ -148,6 +150,15 @@ hipError_t mq_recv_outcomes(uint32_t n_dgrams, uint32_t max_pkts, uint32_t n_con
                             size_t open_ws_bytes, hipStream_t s);
 hipError_t mq_launch_record_inner(const uint8_t* arena, uint64_t arena_len, const mq_pkt_desc* desc, uint32_t n,
                                   uint8_t* status, uint64_t* info, hipStream_t s);
+size_t mq_route_workspace(uint32_t n);  // mq_route.hip
+hipError_t mq_launch_route(const mq::CidTableDev& t, const uint8_t* arena, uint64_t arena_len, mq_dgram* dg, uint32_t n,
+                           uint32_t sdl, const mq_route_admit* admit, uint8_t* status, void* workspace,
+                           hipStream_t s);
+hipError_t mq_launch_cid_insert(const mq::CidTableDev& t, const uint8_t* cids, const uint8_t* lens,
+                                const uint32_t* conn, uint32_t n, uint8_t* status, hipStream_t s);
+hipError_t mq_launch_cid_remove(const mq::CidTableDev& t, const uint8_t* cids, const uint8_t* lens, uint32_t n,
+                                uint8_t* status, hipStream_t s);
+hipError_t mq_launch_cid_compact(const mq::CidTableDev& t, void* to, hipStream_t s);
 int mq_resident_call(int dev, const mq::ResReq& q, uint64_t uid, const uint8_t* aad, const uint8_t* body, uint8_t* out,
                      size_t out_off, size_t out_len, int* status, uint32_t* mask);
 #ifdef MQ_STAMPS
@@ -634,6 +645,16 @@ struct mq_keytable {
       if (suite[r] != MQ_SUITE_AES128GCM) return r;
     return -1;
   }
+};
+
+// Device-resident connection-ID table (mq_route.hip): the slots, a second buffer of the same size
+// that mq_cid_table_compact rehashes into (allocated on first use; the two then swap roles), and the
+// two counters.
+struct mq_cid_table {
+  mq::CidTableDev d = {};
+  mq::CidSlot* spare = nullptr;
+  int device = -1;
+  size_t bytes() const { return sizeof(mq::CidSlot) * ((size_t)d.slot_mask + 1); }
 };
 
 // the host view of rows [first, first + n) after a write (suite_of(i): row first + i's new suite)
@@ -1323,6 +1344,120 @@ int mq_batch_recv(const mq_keytable* kt, mq_conn_recv* conns, uint32_t n_conns, 
   // its bytes as received. Statuses land in the st1 scratch.
   return batch(false, kt, arena, arena_len, p.d1, max_pkts, p.st1, nullptr, MQ_SUITE_MIXED, p.open_ws, stream, true,
                p.live1);
+}
+
+// ---- datagram routing: connection-ID table and admission (mq_route.hip) ------------------------
+int mq_cid_table_create(uint32_t capacity, const uint8_t seed[16], mq_cid_table** out) {
+  if (!out || !seed || capacity > (1u << 30)) return MQ_ERR_INVALID_ARG;
+  *out = nullptr;
+  const int dev = creation_device();
+  if (dev < 0) return MQ_ERR_NO_DEVICE;
+  DeviceGuard g(dev);
+  if (!g.ok()) return MQ_ERR_NO_DEVICE;
+  mq_cid_table* t = new mq_cid_table();
+  t->device = dev;
+  uint64_t slots = 16;  // a power of two >= 2 x capacity: probe chains stay short at full capacity
+  while (slots < 2ull * capacity) slots <<= 1;
+  t->d.slot_mask = (uint32_t)(slots - 1);
+  t->d.capacity = capacity;
+  std::memcpy(&t->d.k0, seed, 8);
+  std::memcpy(&t->d.k1, seed + 8, 8);
+  t->d.hash_mask = (1ull << mq::kCidHashBits) - 1;
+  if (hipMalloc(&t->d.slots, t->bytes()) != hipSuccess || hipMalloc(&t->d.ctr, 256) != hipSuccess ||
+      hipMemset(t->d.slots, 0xFF, t->bytes()) != hipSuccess ||  // every slot empty
+      hipMemset(t->d.ctr, 0, 256) != hipSuccess || hipDeviceSynchronize() != hipSuccess) {
+    mq_cid_table_free(t);
+    return MQ_ERR_HIP;
+  }
+  *out = t;
+  return MQ_OK;
+}
+
+void mq_cid_table_free(mq_cid_table* t) {
+  if (!t) return;
+  {
+    DeviceGuard g(t->device);
+    if (t->d.slots) (void)hipFree(t->d.slots);
+    if (t->spare) (void)hipFree(t->spare);
+    if (t->d.ctr) (void)hipFree(t->d.ctr);
+  }
+  delete t;
+}
+
+int mq_cid_table_insert(mq_cid_table* t, const uint8_t* cids, const uint8_t* lens, const uint32_t* conn, uint32_t n,
+                        uint8_t* status, void* stream) {
+  if (!t || (n && (!cids || !lens || !conn || !status))) return MQ_ERR_INVALID_ARG;
+  DeviceGuard g(t->device);
+  if (!g.ok()) return MQ_ERR_NO_DEVICE;
+  if (n == 0) return MQ_OK;
+  return mq_launch_cid_insert(t->d, cids, lens, conn, n, status, (hipStream_t)stream) == hipSuccess ? MQ_OK
+                                                                                                     : MQ_ERR_HIP;
+}
+
+int mq_cid_table_remove(mq_cid_table* t, const uint8_t* cids, const uint8_t* lens, uint32_t n, uint8_t* status,
+                        void* stream) {
+  if (!t || (n && (!cids || !lens || !status))) return MQ_ERR_INVALID_ARG;
+  DeviceGuard g(t->device);
+  if (!g.ok()) return MQ_ERR_NO_DEVICE;
+  if (n == 0) return MQ_OK;
+  return mq_launch_cid_remove(t->d, cids, lens, n, status, (hipStream_t)stream) == hipSuccess ? MQ_OK : MQ_ERR_HIP;
+}
+
+int mq_cid_table_compact(mq_cid_table* t, void* stream) {
+  if (!t) return MQ_ERR_INVALID_ARG;
+  DeviceGuard g(t->device);
+  if (!g.ok()) return MQ_ERR_NO_DEVICE;
+  if (!t->spare && hipMalloc(&t->spare, t->bytes()) != hipSuccess) return MQ_ERR_HIP;
+  if (mq_launch_cid_compact(t->d, t->spare, (hipStream_t)stream) != hipSuccess) return MQ_ERR_HIP;
+  std::swap(t->d.slots, t->spare);  // later calls (same stream) use the rehashed buffer
+  return MQ_OK;
+}
+
+int mq_cid_table_stats(const mq_cid_table* t, void* stream, uint32_t* live, uint32_t* tombstones, uint32_t* slots) {
+  if (!t) return MQ_ERR_INVALID_ARG;
+  DeviceGuard g(t->device);
+  if (!g.ok()) return MQ_ERR_NO_DEVICE;
+  uint32_t c[2] = {0, 0};
+  if (hipMemcpyAsync(c, t->d.ctr, sizeof c, hipMemcpyDeviceToHost, (hipStream_t)stream) != hipSuccess ||
+      hipStreamSynchronize((hipStream_t)stream) != hipSuccess)
+    return MQ_ERR_HIP;
+  if (live) *live = c[0];
+  if (tombstones) *tombstones = c[1];
+  if (slots) *slots = t->d.slot_mask + 1;
+  return MQ_OK;
+}
+
+int mq_debug_cid_table_hash_bits(mq_cid_table* t, uint32_t bits) {
+  if (!t || bits == 0 || bits > 64) return MQ_ERR_INVALID_ARG;
+  DeviceGuard g(t->device);
+  if (!g.ok()) return MQ_ERR_NO_DEVICE;
+  uint32_t c[2] = {0, 0};
+  if (hipDeviceSynchronize() != hipSuccess || hipMemcpy(c, t->d.ctr, sizeof c, hipMemcpyDeviceToHost) != hipSuccess)
+    return MQ_ERR_HIP;
+  if (c[0] || c[1]) return MQ_ERR_INVALID_ARG;  // entries hashed with the old mask would be lost
+  t->d.hash_mask = (1ull << (bits < mq::kCidHashBits ? bits : mq::kCidHashBits)) - 1;
+  return MQ_OK;
+}
+
+size_t mq_batch_route_workspace_size(uint32_t n_dgrams) { return mq_route_workspace(n_dgrams); }
+
+int mq_batch_route(mq_cid_table* t, const uint8_t* arena, uint64_t arena_len, mq_dgram* dgrams, uint32_t n_dgrams,
+                   uint32_t short_dcid_len, const mq_route_admit* admit, uint8_t* status, void* workspace,
+                   void* stream) {
+  if (short_dcid_len > mq::kRouteMaxCid || n_dgrams > (1u << 30)) return MQ_ERR_INVALID_ARG;
+  if (admit) {
+    if ((uint64_t)admit->conn_base + admit->max_new > admit->n_conns || !admit->n_new) return MQ_ERR_INVALID_ARG;
+    if (admit->max_new && (!admit->conns || !admit->new_dcids || !admit->new_dcid_lens)) return MQ_ERR_INVALID_ARG;
+  }
+  if (!t || (n_dgrams && (!arena || !dgrams || !status || (admit && !workspace)))) return MQ_ERR_INVALID_ARG;
+  if (((uintptr_t)workspace & 15) != 0 || ((uintptr_t)dgrams & 15) != 0) return MQ_ERR_INVALID_ARG;
+  DeviceGuard g(t->device);
+  if (!g.ok()) return MQ_ERR_NO_DEVICE;
+  if (n_dgrams == 0 && !admit) return MQ_OK;
+  return mq_launch_route(t->d, arena, arena_len, dgrams, n_dgrams, short_dcid_len, admit, status, workspace,
+                         (hipStream_t)stream) == hipSuccess
+             ? MQ_OK
+             : MQ_ERR_HIP;
 }
 
 // ---- TLS 1.3 records (tcp_tls/record.rs:88-143, connection.rs:546-600) -----------------------

@@ -12,7 +12,11 @@ stream; median of `reps`). Prints one JSON object; the round's copy lives in pro
   rekey    mq_batch_derive_keys / mq_batch_key_update: 2^20 traffic secrets -> rows, per suite; a
            4096-row sample of the key material byte-checked against the host functions; the host
            path (HKDF per row + one mq_keytable_update) over 2^14 of the same rows
-Usage: python tools/bench_aux.py [reps] | rekey [reps] | recv reps conns...
+  route    mq_batch_route over 2^20 x 1200-B datagrams: all hits over 4096 connections (with
+           mq_batch_recv over the same batch), all hits over 2^20 connections (a 64-MiB table), and an
+           Initial flood of 2^20 distinct new DCIDs with max_new = 2^20 (with mq_batch_derive_initial
+           over what it admitted); 4096 datagrams of each run checked against tests/route_model.py
+Usage: python tools/bench_aux.py [reps] | rekey [reps] | recv reps conns... | route [reps]
 """
 import json
 import os
@@ -221,7 +225,157 @@ def bench_rekey(reps, suite, n=1 << 20, n_host=1 << 14, k=4096):
     return out
 
 
+def route_sample_check(table_cids, table_conns, arena, dg, st, conn, sdl, idx, admit=None):
+    """Datagrams idx of a timed route run against the Python model (tests/route_model.py), which gets
+    their bytes and the table entries they can hit."""
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
+    import route_model
+    L = int(dg["len"][0])
+    model = route_model.TableModel(1 << 30)
+    model.map = dict(zip(table_cids, table_conns))
+    rows = arena.view(-1, L)[torch.from_numpy(idx.astype(np.int64)).to(DEV)].cpu().numpy()
+    sub = np.zeros(len(idx), dtype=recv.DGRAM_DTYPE)
+    sub["offset"], sub["len"] = np.arange(len(idx), dtype=np.uint64) * np.uint64(L), L
+    adm = None
+    if admit is not None:
+        adm = route_model.AdmitModel(np.zeros(len(idx), dtype=recv.CONN_DTYPE), 0, len(idx), admit, L)
+    want_st, want_conn = model.route(rows.reshape(-1), sub, sdl, adm)
+    got_st, got_conn = st.cpu().numpy()[idx], conn[idx]
+    assert (got_st == want_st).all() and (got_conn == want_conn).all(), "route sample differs from the model"
+    return len(idx)
+
+
+def bench_route(reps, n=1 << 20, L=1200, k=4096):
+    from milli_quic_amd import route
+    seed = bytes(range(16))
+    res = {}
+    i = np.arange(n, dtype=np.uint64)
+    pick = np.sort(np.random.default_rng(12).choice(n, size=k, replace=False))
+
+    def dgrams(conn_fill):
+        dg = np.zeros(n, dtype=recv.DGRAM_DTYPE)
+        dg["offset"], dg["len"], dg["conn"] = i * np.uint64(L), L, conn_fill
+        return dg
+
+    def fill(table, cids8, n_conns):
+        c20 = np.zeros((n_conns, 20), dtype=np.uint8)
+        c20[:, :8] = cids8
+        st = torch.full((n_conns,), 0xEE, dtype=torch.uint8, device=DEV)
+        table.insert(t(c20), torch.full((n_conns,), 8, dtype=torch.uint8, device=DEV),
+                     torch.arange(n_conns, dtype=torch.int32, device=DEV), st)
+        torch.cuda.synchronize()
+        assert int((st != 0).sum()) == 0
+        assert table.stats()[0] == n_conns
+
+    # ---- all hits over 4096 connections: real 1-RTT packets, so that mq_batch_recv runs on what
+    # ---- the route call filled in
+    n_conns, fl = 4096, 1171
+    w = workload.uniform(64, _lib.MQ_SUITE_CHACHA20, n_keys=n_conns)
+    kt = KeyTable(w.keys)
+    cids = workload.splitmix_bytes(8 * n_conns, seed=21).reshape(n_conns, 8)
+    conns = send.make_conns([c.tobytes() for c in cids], [b""] * n_conns, [[c, c, c] for c in range(n_conns)])
+    req = np.zeros(n, dtype=send.REQ_DTYPE)
+    req["frames_offset"], req["out_offset"] = i * np.uint64(fl), i * np.uint64(L)
+    req["pn"] = np.uint64(0x10000000) + i // np.uint64(n_conns)
+    req["largest_acked"] = req["pn"] - np.uint64(1 << 24)
+    req["frame_len"], req["out_cap"], req["level"] = fl, L, send.APPLICATION
+    req["conn"] = (i % np.uint64(n_conns)).astype(np.uint32)
+    frames = t(workload.splitmix_bytes(n * fl, seed=3))
+    out = torch.zeros(n * L, dtype=torch.uint8, device=DEV)
+    st = torch.zeros(n, dtype=torch.uint8, device=DEV)
+    ln = torch.zeros(n, dtype=torch.int32, device=DEV)
+    ws = torch.empty(send.workspace_bytes(n), dtype=torch.uint8, device=DEV)
+    send.protect(kt, t(conns), frames, out, t(req), st, ln, _lib.MQ_SUITE_CHACHA20, ws)
+    torch.cuda.synchronize()
+    assert int((st != 0).sum()) == 0
+    del frames, ws
+    sealed = out.clone()
+    table = route.CidTable(n_conns, seed)
+    fill(table, cids, n_conns)
+    dgt = t(dgrams(0xDEAD))
+    ms = timed(lambda: route.route(table, out, dgt, st, 8), reps)
+    got = dgt.cpu().numpy().view(recv.DGRAM_DTYPE)["conn"]
+    assert int((st != 0).sum()) == 0 and (got == req["conn"]).all()
+    checked = route_sample_check([c.tobytes() for c in cids], range(n_conns), out, dgrams(0), st, got, 8, pick)
+    rc = np.zeros(n_conns, dtype=recv.CONN_DTYPE)
+    rc["app_row"][:, 1] = np.arange(n_conns)
+    rc["dcid_len"], rc["flags"] = 8, recv.HAS_APP
+    pk = torch.zeros(n * 32, dtype=torch.uint8, device=DEV)
+    cnt = torch.zeros(1, dtype=torch.int32, device=DEV)
+    rws = torch.empty(recv.workspace_bytes(n, n, n_conns), dtype=torch.uint8, device=DEV)
+    ct0 = t(rc)
+    ct = ct0.clone()
+    copy_ms = timed(lambda: (out.copy_(sealed), ct.copy_(ct0)), reps)
+    ms_r = timed(lambda: (out.copy_(sealed), ct.copy_(ct0), recv.recv(kt, ct, out, dgt, pk, cnt, rws)), reps) - copy_ms
+    assert int(cnt[0]) == n and (pk.cpu().numpy().view(recv.PKT_DTYPE)["status"] == 0).all()
+    res["hits_4096_connections"] = {
+        "datagrams": n, "connections": n_conns, "route_ms": round(ms, 4), "Mdgrams_per_s": round(n / ms / 1e3, 1),
+        "recv_ms": round(ms_r, 4), "route_over_recv": round(ms / ms_r, 4), "sample_checked": checked}
+    del sealed, pk, rws, kt, table
+
+    # ---- all hits over 2^20 connections (2^21 slots of 32 B = 64 MiB), datagram i -> a random connection
+    n_conns = n
+    cids = workload.splitmix_bytes(8 * n_conns, seed=22).reshape(n_conns, 8)
+    perm = np.random.default_rng(5).permutation(n_conns).astype(np.uint32)
+    rows = out.view(n, L)
+    rows[:, 0] = 0x41
+    rows[:, 1:9] = t(cids[perm]).view(n, 8)
+    table = route.CidTable(n_conns, seed)
+    fill(table, cids, n_conns)
+    dgt = t(dgrams(0xDEAD))
+    ms = timed(lambda: route.route(table, out, dgt, st, 8), reps)
+    got = dgt.cpu().numpy().view(recv.DGRAM_DTYPE)["conn"]
+    assert int((st != 0).sum()) == 0 and (got == perm).all()
+    sub = {cids[perm[j]].tobytes(): int(perm[j]) for j in pick}
+    checked = route_sample_check(list(sub), list(sub.values()), out, dgrams(0), st, got, 8, pick)
+    res["hits_1M_connections"] = {
+        "datagrams": n, "connections": n_conns, "table_MiB": table.stats()[2] * 32 >> 20, "route_ms": round(ms, 4),
+        "Mdgrams_per_s": round(n / ms / 1e3, 1), "route_over_recv_4096": round(ms / ms_r, 4), "sample_checked": checked}
+    del table
+
+    # ---- Initial flood: every datagram the first Initial of a new connection -----------------------
+    hdr = np.zeros((n, 14), dtype=np.uint8)
+    hdr[:, 0], hdr[:, 4], hdr[:, 5] = 0xC3, 1, 8
+    hdr[:, 6:14] = cids[perm]
+    rows[:, :14] = t(hdr).view(n, 14)
+    d_conns = torch.zeros(n * recv.CONN_DTYPE.itemsize, dtype=torch.uint8, device=DEV)
+    new_dcids = torch.zeros(20 * n, dtype=torch.uint8, device=DEV)
+    new_lens = torch.zeros(n, dtype=torch.uint8, device=DEV)
+    n_new = torch.zeros(1, dtype=torch.int32, device=DEV)
+    admit = route.Admit(d_conns, 0, n, 0, new_dcids, new_lens, n_new)
+    rws = torch.empty(route.workspace_bytes(n), dtype=torch.uint8, device=DEV)
+    times = []
+    for _ in range(reps + 1):  # an empty table per run (created outside the timed span)
+        table = route.CidTable(n, seed)
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        route.route(table, out, dgt, st, 8, workspace=rws, admit=admit)
+        e1.record()
+        torch.cuda.synchronize()
+        times.append(e0.elapsed_time(e1))
+    ms = float(np.median(times[1:]))
+    got = dgt.cpu().numpy().view(recv.DGRAM_DTYPE)["conn"]
+    assert int(n_new[0]) == n and int((st != route.NEW).sum()) == 0 and (got == i.astype(np.uint32)).all()
+    assert table.stats()[0] == n
+    assert new_dcids.view(n, 20)[:, :8].cpu().numpy().tobytes() == cids[perm].tobytes()
+    # a prefix is self-contained (ranks count the new DCIDs before each datagram)
+    checked = route_sample_check([], [], out, dgrams(0), st, got, 8, np.arange(k), admit=0)
+    kt = KeyTable([_lib.KeyMaterial() for _ in range(2 * n)])
+    dst = torch.zeros(n, dtype=torch.uint8, device=DEV)
+    ms_d = timed(lambda: batch.derive_initial(kt, 0, new_dcids, new_lens, dst), reps)
+    assert int((dst != 0).sum()) == 0
+    res["initial_flood"] = {
+        "datagrams": n, "new_connections": n, "route_ms": round(ms, 4), "Mdgrams_per_s": round(n / ms / 1e3, 1),
+        "derive_initial_ms": round(ms_d, 4), "route_over_derive": round(ms / ms_d, 4), "sample_checked": checked}
+    return res
+
+
 def main():
+    if len(sys.argv) > 1 and sys.argv[1] == "route":  # routing runs only: route [REPS]
+        assert _lib.load().mq_device_init(0) == 0
+        reps = int(sys.argv[2]) if len(sys.argv) > 2 else 5
+        print(json.dumps({"device": torch.cuda.get_device_name(0), "route": bench_route(reps)}), flush=True)
+        return
     if len(sys.argv) > 1 and sys.argv[1] == "rekey":  # key derivation / update runs only: rekey [REPS]
         assert _lib.load().mq_device_init(0) == 0
         reps = int(sys.argv[2]) if len(sys.argv) > 2 else 5
@@ -250,6 +404,7 @@ def main():
     res["hp_mask_chacha"] = bench_hp_mask(reps, _lib.MQ_SUITE_CHACHA20)
     res["rekey_aes"] = bench_rekey(reps, _lib.MQ_SUITE_AES128GCM)
     res["rekey_chacha"] = bench_rekey(reps, _lib.MQ_SUITE_CHACHA20)
+    res["route"] = bench_route(reps)
     print(json.dumps(res), flush=True)
 
 
