@@ -8,7 +8,8 @@
 // Per tile (8 packets, one octet of lanes per packet; see mq_tile.h):
 //   seal: keystream block ctr on lane ctr % 8 (ctr 0 = Poly1305 one-time key) XORed into LDS
 //         (blocks >= 16 and the header-protection block through the workgroup's keystream pool)
-//         -> interleaved Poly1305 over AAD||pad||CT||pad||lens -> tag -> header mask applied
+//         -> interleaved Poly1305 over AAD||pad||CT||pad||lens (per wave, 8 lanes per packet; in
+//         the flat 10-KiB kernels as a workgroup phase, 4 lanes per packet) -> tag -> header mask applied
 //   open: HP mask -> unmask byte 0 / PN -> decode_pn -> nonce -> first keystream block (lane 0:
 //         one-time key) -> Poly1305 over the untouched ciphertext -> tag check -> only then the
 //         keystream XOR (held first block + the rest); failed packets are never stored.
@@ -242,15 +243,21 @@ constexpr uint32_t kCcPoolSlot = kCcOwnIters * kLanesPerPkt;  // first pooled sl
 // the batch (r02 ran it as a post-pass kernel: 63 us and 0.23 GB per 2^20 packets). The mask waits
 // in the record until the MAC has read the unprotected header; octet lane 0 then applies it.
 //
-// this packet's 32-B pool record in its wave's scratch: [0] pooled keystream blocks | the PN
-// length << 8 when the header-protection block is pooled too, [1] payload LDS offset (workgroup)
-// | P << 17, [2] / [7] mask words 0 / 1 (written by the pool), [3] key row, [4..6] nonce words
+// this packet's 32-B pool record in its wave's scratch: [0] pooled keystream blocks (bits 0-7) | the
+// PN length << 8 (3 bits) when the header-protection block is pooled too | for the workgroup MAC
+// (cc_wg_mac) the AAD length << 11 (14 bits: a staged packet is under 16 KiB) and kCcRecMac,
+// [1] payload LDS offset (workgroup) | P << 17, [2] / [7] mask words 0 / 1 (written by the pool;
+// open pools no mask: [2] is the MAC's verdict, tag XOR received tag), [3] key row, [4..6] nonce words
+constexpr uint32_t kCcRecMac = 0x80000000u;  // the packet waits for the workgroup MAC
+constexpr uint32_t kCcRecAadShift = 11, kCcRecAadMask = 0x3fffu;
 struct CcPool {
   bool on;              // wave-uniform: staged tile whose slots >= 16 go to the pool
   uint8_t* wg;          // the workgroup's LDS
   uint32_t base;        // this wave's region in it
   uint32_t* rec;        // this packet's record
   const KeyRow* kt;
+  uint32_t role;        // this wave's role in the pool and the MAC phase: its index, or rotated (chacha_tile)
+  bool mac;             // workgroup-uniform: the MAC runs as a workgroup phase (cc_wg_mac)
 };
 
 // IMG: bytes of LDS per wave (kLdsBytes; the long-packet kernels' larger images, chacha_tile);
@@ -260,16 +267,17 @@ struct CcPool {
 // Sp: the LDS space of the workgroup's staged tiles (LdsSpace, or LdsSpaceRaw: the raw-dword XOR)
 template <bool SINGLE, uint32_t IMG = kLdsBytes, uint32_t W = kCcWaves, bool R1 = false, class Sp = LdsSpace>
 __device__ __forceinline__ void cc_pool_run(const CcPool& pool, uint32_t tid = threadIdx.x) {
+  // role r takes the pool's wave-iterations r, r + W, ...
   static_assert(SINGLE || !R1, "round one is hoisted for wave-uniform keys only");
   constexpr uint32_t kQ = kPktsPerTile * W;  // packets of the workgroup
   static_assert(kQ <= kWave, "one packet per lane in the pool scan");
   const int lane = tid & (kWave - 1);
-  const uint32_t w = tid >> 6;
+  const uint32_t w = pool.role;
   auto rec = [&](uint32_t q) -> uint32_t* {
     return (uint32_t*)(pool.wg + (q >> 3) * IMG + (IMG - kScratchBytes) + 32u * (q & 7));
   };
   const uint32_t r0l = (uint32_t)lane < kQ ? rec((uint32_t)lane)[0] : 0u;  // lane q: packet q
-  const uint32_t nq = (r0l & 0xffu) + ((r0l >> 8) ? 1u : 0u);
+  const uint32_t nq = (r0l & 0xffu) + ((r0l >> 8 & 7u) ? 1u : 0u);
   const uint32_t incl = wave_incl_scan(nq), excl = incl - nq;
   const uint32_t T = lane_u32(incl, kWave - 1);
   Sp sp{};
@@ -286,7 +294,7 @@ __device__ __forceinline__ void cc_pool_run(const CcPool& pool, uint32_t tid = t
     const bool act = e < T;
     uint32_t* r = rec(q);
     const uint32_t r0 = r[0], r1 = r[1], pay = r1 & 0x1ffffu, P = r1 >> 17;
-    const uint32_t idx = e - eq, pn_len = r0 >> 8;
+    const uint32_t idx = e - eq, pn_len = r0 >> 8 & 7u;
     const bool hp = !R1 && act && idx == (r0 & 0xffu);  // the packet's last entry: its HP block
     const uint32_t cb = kCcPoolSlot + idx, o = kKsStride * (cb - 1);
     const KeyRow* row = SINGLE || !act ? pool.kt : pool.kt + r[3];  // an idle lane's record may be stale
@@ -323,6 +331,45 @@ __device__ __forceinline__ void cc_pool_run(const CcPool& pool, uint32_t tid = t
 // the pool's space for a tile code running on S (the direct path's tiles pool nothing)
 template <class S> struct PoolSpace { typedef LdsSpace type; };
 template <> struct PoolSpace<LdsSpaceRaw> { typedef LdsSpaceRaw type; };
+
+// ---- MAC phase of a workgroup (the flat octet-tile kernels, chacha_tile) ------------------------
+// The per-packet fixed part of the interleaved Poly1305 (the powers of r, the edge steps, the final
+// multiply, the group sum and the finish: about 630 of a 1200-B tile's 1120 VALU) is paid per
+// wave-instruction stream, which covers 64 / G packets. Between two barriers the MAC of the
+// workgroup's 32 packets therefore runs on two waves with G = 4 lanes per packet, 16 packets each,
+// instead of on four waves with G = 8: MAC wave m takes packets 16 m .. 16 m + 15 (lane 4 q' + j:
+// packet 16 m + q', group lane j). What it needs of a packet waits in the pool record (CcPool) and,
+// the one-time key, in the packet's scratch; addresses are the workgroup's. Seal: group lane 0
+// stores the tag behind the payload. Open: it writes the verdict (tag XOR received tag) into the
+// record and, for a packet that fails, clears the record's pooled blocks, so nothing of it is
+// decrypted. The lean stretch's look-ahead reads (poly_tag) end in the next image or in a wave's
+// scratch: inside the workgroup's allocation.
+template <bool OPEN, uint32_t IMG, uint32_t W>
+__device__ __forceinline__ void cc_wg_mac(uint8_t* wg, uint32_t m, uint32_t tid) {
+  constexpr int G = 4;
+  static_assert(kPktsPerTile * W == 2 * (kWave / G), "two MAC waves of 16 packets");
+  const int lane = tid & (kWave - 1), j = lane % G;
+  const uint32_t q = (kWave / G) * m + (uint32_t)lane / G;
+  uint32_t* rec = (uint32_t*)(wg + (q >> 3) * IMG + (IMG - kScratchBytes) + 32u * (q & 7));
+  const uint32_t r0 = rec[0], r1 = rec[1];
+  const bool act = (r0 & kCcRecMac) != 0;  // else the record's other words may be stale
+  const uint32_t aad_len = act ? r0 >> kCcRecAadShift & kCcRecAadMask : 0u;
+  const uint32_t pay = act ? r1 & 0x1ffffu : 0u, P = act ? r1 >> 17 : 0u;
+  LdsSpace sp{wg};
+  uint32_t tag[4];
+  poly_tag<G>(sp, pay - aad_len, pay, aad_len, P, OtkLds{rec + 8 * kPktsPerTile}, j, act, tag);  // the key: 8 records on
+  if (OPEN) {
+    uint32_t got[4];
+    load_words<4>(sp, pay + P, got);
+    const uint32_t diff = (tag[0] ^ got[0]) | (tag[1] ^ got[1]) | (tag[2] ^ got[2]) | (tag[3] ^ got[3]);
+    if (act && j == 0) {
+      rec[2] = diff;
+      if (diff) rec[0] = 0;
+    }
+  } else if (act && j == 0) {
+    store_words<4>(sp, pay + P, tag);
+  }
+}
 
 // The tile code of both layouts: octet tiles (8 lanes per packet, the keystream pool; chacha_tile,
 // chacha_protect_tile) and narrow tiles (G = 1, 2, 4 or 8 lanes per packet, no pool; narrow_tile).
@@ -414,13 +461,13 @@ struct ChaChaPolicy {
   // What both end with: the tag behind the payload, then header protection (transmit.rs:713-738)
   // now that the MAC has read the unprotected header. have: the packet's mask (m0, m1) was made in
   // a keystream slot and is on group lane jh; the other packets' masks this wave computes late, on
-  // every lane of the group.
+  // every lane of the group. store_tag false: the workgroup MAC has stored the tag.
   template <class S>
   static __device__ __forceinline__ void seal_finish(const S& sp, typename S::off_t pkt, const PktCtx& c,
                                                      const KeyRow* row, int j, const SealPkt<S>& k,
                                                      const uint32_t (&tag)[4], bool have, int jh, uint32_t m0,
-                                                     uint32_t m1) {
-    if (c.act && j == 0) store_words<4>(sp, k.pay + k.P, tag);
+                                                     uint32_t m1, bool store_tag = true) {
+    if (store_tag && c.act && j == 0) store_words<4>(sp, k.pay + k.P, tag);
     const bool late = k.hp && !have;
     if (wave_any(late)) {
       wave_sync();  // ciphertext and tags are in place
@@ -441,7 +488,11 @@ struct ChaChaPolicy {
   // header-protection block (its sample is ciphertext of block 1) run in the workgroup's pool
   // before the MACs, and the mask is applied once the MAC has read the unprotected header.
   // R1: round one's wave-uniform part hoisted (single-key kernels; chacha_tile says which)
-  template <bool SINGLE, uint32_t IMG = kLdsBytes, uint32_t W = kCcWaves, bool R1 = false, class S, class St>
+  // WG: the kernel has the workgroup MAC phase (cc_wg_mac), taken when pool.mac says so: a staged
+  // tile hands its packets over in their records; a direct-path tile MACs itself, as without the
+  // phase, but runs the phase's barrier and its role
+  template <bool SINGLE, uint32_t IMG = kLdsBytes, uint32_t W = kCcWaves, bool R1 = false, bool WG = false, class S,
+            class St>
   static __device__ __forceinline__ void seal(const S& sp, typename S::off_t pkt, PktCtx& c, const KeyRow* row, int j,
                                               St& stg, const CcPool& pool) {
     const mq_pkt_desc& d = c.d;
@@ -492,11 +543,14 @@ struct ChaChaPolicy {
     // the pool takes the HP block when the sample (payload bytes [4 - pn_len, 20 - pn_len)) is all
     // ciphertext; for tiny payloads it reaches into the tag, which only the MAC below produces
     const bool hp_pool = pool.on && k.hp && P + d.pn_len >= 20u;
-    if (j == 0) {  // pool record: keystream blocks >= 16 and the HP block
+    const bool wgm = WG && pool.mac;                 // workgroup-uniform
+    const bool handed = wgm && pool.on;              // wave-uniform: the workgroup MACs this tile
+    if (j == 0) {  // pool record: keystream blocks >= 16 and the HP block; the MAC's inputs
       const uint32_t np = pool.on && c.act && nblk > kCcPoolSlot ? nblk - kCcPoolSlot : 0u;
       const uint32_t hpn = hp_pool ? (uint32_t)d.pn_len : 0u;  // 1..4 (validated)
-      pool.rec[0] = np | hpn << 8;
-      if (np || hpn) {
+      const uint32_t mac = handed && c.act ? kCcRecMac | k.aad_len << kCcRecAadShift : 0u;
+      pool.rec[0] = np | hpn << 8 | mac;
+      if (np || hpn || mac) {
         pool.rec[1] = (pool.base + (uint32_t)pay) | P << 17;
         pool.rec[3] = d.key_id;
         pool.rec[4] = k.n0; pool.rec[5] = k.n1; pool.rec[6] = k.n2;
@@ -506,8 +560,12 @@ struct ChaChaPolicy {
     cc_pool_run<SINGLE, IMG, W, false, typename PoolSpace<S>::type>(pool);
     __syncthreads();  // every pooled block (and mask) is in place before any MAC reads it
     MQ_STAMP(c.tile, 3);
-    uint32_t tag[4];
-    poly_tag<kLanesPerPkt>(sp, pkt, pay, k.aad_len, P, OtkLds{c.otk}, j, c.act, tag);
+    uint32_t tag[4] = {0, 0, 0, 0};
+    if (!handed) poly_tag<kLanesPerPkt>(sp, pkt, pay, k.aad_len, P, OtkLds{c.otk}, j, c.act, tag);
+    if (WG && wgm) {
+      if (pool.role >= W - 2) cc_wg_mac<false, IMG, W>(pool.wg, pool.role - (W - 2), threadIdx.x);
+      __syncthreads();  // every tag is in place
+    }
     // the pooled mask waits in the record; without one (direct path, or a sample that reaches
     // into the tag) the wave computes it late; octet lane 0 applies either
     uint32_t m0 = 0, m1 = 0;
@@ -515,7 +573,7 @@ struct ChaChaPolicy {
       m0 = pool.rec[2];
       m1 = pool.rec[7];
     }
-    seal_finish(sp, pkt, c, row, j, k, tag, hp_pool, 0, m0, m1);
+    seal_finish(sp, pkt, c, row, j, k, tag, hp_pool, 0, m0, m1, !handed);
     MQ_STAMP(c.tile, 4);
   }
 
@@ -600,12 +658,27 @@ struct ChaChaPolicy {
   // through the packet's LDS scratch and keystream blocks >= 16 to the workgroup's pool, both
   // barriers included; else (narrow tiles) the key travels by DPP and the wave runs every block.
   // R1: round one's wave-uniform part hoisted (single-key octet kernels; chacha_tile says which)
-  template <int G, bool POOL, bool SINGLE, uint32_t IMG = kLdsBytes, uint32_t W = kCcWaves, bool R1 = false, class S,
-            class St>
+  // WG: the kernel has the workgroup MAC phase (cc_wg_mac), taken when pool.mac says so. A staged
+  // tile then writes its pool records before the MAC, as if every packet verified (the MAC clears
+  // a failed packet's), hands its packets over between two barriers and takes the verdicts; the
+  // pool follows the wave's own blocks with no barrier of its own. A direct-path tile MACs itself
+  // and runs the same barriers and its role first, while little is live (the role's registers on
+  // top of the direct path's spilled).
+  template <int G, bool POOL, bool SINGLE, uint32_t IMG = kLdsBytes, uint32_t W = kCcWaves, bool R1 = false,
+            bool WG = false, class S, class St>
   static __device__ __forceinline__ void open(const S& sp, typename S::off_t pkt, PktCtx& c, const KeyRow* row, int j,
                                               bool direct, St& stg, const CcPool& pool = CcPool{}) {
     typedef Grp<G> Gp;
     const mq_pkt_desc& d = c.d;
+    constexpr bool kDirect = std::is_same<S, GlobalSpace>::value;
+    if constexpr (WG && POOL && kDirect) {
+      if (pool.mac) {  // nothing to hand over
+        if (j == 0) pool.rec[0] = 0;
+        __syncthreads();
+        if (pool.role >= W - 2) cc_wg_mac<true, IMG, W>(pool.wg, pool.role - (W - 2), threadIdx.x);
+        __syncthreads();
+      }
+    }
     stg.issue();
     uint32_t pn_len = d.pn_len, trunc = 0;
     uint8_t orig_b0 = 0, b0 = 0;
@@ -649,9 +722,21 @@ struct ChaChaPolicy {
     if (POOL) MQ_STAMP(c.tile, 3);
     if (POOL && c.act && j == 0) store_otk(c.otk, ks0);
     wave_sync();
-    uint32_t tag[4], got[4];
+    const bool wgm = WG && POOL && pool.mac;  // workgroup-uniform
+    const bool handed = wgm && !kDirect;       // the workgroup MACs this tile
+    auto pool_record = [&]() {  // octet lane 0. Only verified packets are decrypted (no HP block on open)
+      const uint32_t np = pool.on && c.act && nblk > kCcPoolSlot ? nblk - kCcPoolSlot : 0u;
+      const uint32_t mac = handed && c.act ? kCcRecMac | aad_len << kCcRecAadShift : 0u;
+      pool.rec[0] = np | mac;
+      if (np || mac) {
+        pool.rec[1] = (pool.base + (uint32_t)pay) | P << 17;
+        pool.rec[3] = d.key_id;
+        pool.rec[4] = n0; pool.rec[5] = n1; pool.rec[6] = n2;
+      }
+    };
+    uint32_t tag[4] = {0, 0, 0, 0}, got[4] = {0, 0, 0, 0};
     if (POOL) {
-      poly_tag<G>(sp, pkt, pay, aad_len, P, OtkLds{c.otk}, j, c.act, tag);
+      if (!handed) poly_tag<G>(sp, pkt, pay, aad_len, P, OtkLds{c.otk}, j, c.act, tag);
     } else {
       OtkRegs rs;
 #pragma unroll
@@ -661,8 +746,17 @@ struct ChaChaPolicy {
       }
       poly_tag<G>(sp, pkt, pay, aad_len, P, rs, j, c.act, tag);
     }
-    load_words<4>(sp, pay + P, got);
-    const uint32_t diff = (tag[0] ^ got[0]) | (tag[1] ^ got[1]) | (tag[2] ^ got[2]) | (tag[3] ^ got[3]);
+    if (!handed) load_words<4>(sp, pay + P, got);
+    uint32_t diff = (tag[0] ^ got[0]) | (tag[1] ^ got[1]) | (tag[2] ^ got[2]) | (tag[3] ^ got[3]);
+    if constexpr (WG && POOL && !kDirect) {
+      if (wgm) {
+        if (j == 0) pool_record();
+        __syncthreads();  // every wave's records, keys and unmasked headers
+        if (pool.role >= W - 2) cc_wg_mac<true, IMG, W>(pool.wg, pool.role - (W - 2), threadIdx.x);
+        __syncthreads();  // every verdict; every MAC has read its ciphertext
+        if (handed && c.act) diff = pool.rec[2];
+      }
+    }
     if (c.act && diff != 0) {  // Error::Crypto, buffer left as received
       c.st = MQ_ERR_CRYPTO;
       c.act = false;
@@ -686,16 +780,10 @@ struct ChaChaPolicy {
       if (a) store_block(sp, pay, ctr, P, ks, w);
     }
     if constexpr (POOL) {
-      if (j == 0) {  // pool record: only verified packets are decrypted (no HP block on open)
-        const uint32_t np = pool.on && c.act && nblk > kCcPoolSlot ? nblk - kCcPoolSlot : 0u;
-        pool.rec[0] = np;
-        if (np) {
-          pool.rec[1] = (pool.base + (uint32_t)pay) | P << 17;
-          pool.rec[3] = d.key_id;
-          pool.rec[4] = n0; pool.rec[5] = n1; pool.rec[6] = n2;
-        }
+      if (!wgm) {
+        if (j == 0) pool_record();
+        __syncthreads();  // every wave's MAC has read its ciphertext
       }
-      __syncthreads();  // every wave's MAC has read its ciphertext
       cc_pool_run<SINGLE, IMG, W, R1, typename PoolSpace<S>::type>(pool);
       __syncthreads();
       MQ_STAMP(c.tile, 5);
@@ -869,8 +957,9 @@ __device__ __forceinline__ void narrow_tile(uint8_t* wsm, const KeyRow* __restri
 using namespace mq;
 
 // Tile kernels: one tile per wave, each with its private 10 KiB LDS image, kCcWaves-wave
-// workgroups sharing the keystream pool above between two barriers. Every wave of a workgroup
-// runs both barriers: waves past the batch with an empty record, direct-path tiles (images over
+// workgroups sharing the keystream pool above between two barriers (and, in the flat 10-KiB
+// kernels, the MAC phase, cc_wg_mac, between two more). Every wave of a workgroup
+// runs every barrier: waves past the batch with an empty record, direct-path tiles (images over
 // the budget) with nothing pooled. (A persistent grid walking
 // tiles, as the AES kernels use, measured 10 % slower here: identical waves stay in phase, so
 // their staging waits line up.) The "1" variants are launched when the key table has a single
@@ -913,6 +1002,33 @@ __device__ __forceinline__ void chacha_narrow_list(uint8_t* wsm, uint32_t u, con
 // waves run their tile first), one without any runs its narrow tiles with no barrier.
 // n_rows carries the MQ_CC_SPAN=0 switch in its top bit (a key table never has 2^31 rows).
 constexpr uint32_t kCcNoSpan = 0x80000000u;
+// and, one bit down, the MQ_CC_WGMAC=0 switch: the per-wave MAC in the kernels that have the
+// workgroup MAC phase
+constexpr uint32_t kCcNoWgMac = 0x40000000u;
+// Roles of a workgroup's waves: role = (w + h) & 3. The pool's wave-iterations fall on roles 0, 1
+// and, for seal, 2, the MAC phase on the last two roles, which carry the least pool work (open:
+// none; seal: none and the half-filled iteration with the header-protection blocks). Wave w of a
+// workgroup usually sits on SIMD w, so h decides which SIMDs of a CU carry which phase, and the two
+// kernels want opposite things (config B, ms per 2^20 packets, profiles/r11_ab_rotation_b.txt;
+// parent: seal 0.920, open 0.909):
+//                                          seal    open
+//   h = 0                                  0.891   0.959
+//   h = block >> 8                         1.065   0.894
+//   h = top bits of block * 0x9E3779B1     0.937   0.944
+// Seal runs pool then MAC: with h = 0 the workgroups of a CU that are in different phases use
+// different SIMDs. Open runs the MAC first, beside other workgroups' staging waits; there the four
+// workgroups that share a CU want four different rotations, and under round-robin dispatch over
+// 256 CUs those are blocks 256 apart. Neither mapping is promised by the hardware: no result
+// depends on h, only the time. -DMQ_CC_ROLE_FIXED builds h = 0 for both.
+template <bool OPEN>
+__device__ __forceinline__ uint32_t cc_role(uint32_t tb, uint32_t w, uint32_t W) {
+#ifdef MQ_CC_ROLE_FIXED
+  (void)tb;
+  return w & (W - 1);
+#else
+  return (w + (OPEN ? tb >> 8 : 0u)) & (W - 1);
+#endif
+}
 // SPAN = false: no span tiles in this kernel, whatever the switch says (chacha_list).
 template <bool OPEN, bool SINGLE, bool LIST = false, uint32_t IMG = kLdsBytes, uint32_t W = kCcWaves, bool SPAN = true>
 __device__ __forceinline__ void chacha_tile(uint32_t tb, uint32_t tid, const KeyRow* __restrict__ kt, uint32_t n_rows,
@@ -934,12 +1050,16 @@ __device__ __forceinline__ void chacha_tile(uint32_t tb, uint32_t tid, const Key
   // list kernels (SPAN = false) nor in the fused protect tile: there it costs scratch (seal list
   // 40 -> 44 B per lane, open list 0 -> 20, protect 0 -> 8)
   constexpr bool kR1 = SINGLE && SPAN;
+  // The workgroup MAC phase (cc_wg_mac) and the rotating roles: the flat kernels over 10-KiB images
+  constexpr bool kWg = SPAN && !LIST && IMG == kLdsBytes && W == 4;
   const bool span_ok = SPAN && (n_rows & kCcNoSpan) == 0;
-  n_rows &= ~kCcNoSpan;
+  const bool wgm = kWg && (n_rows & kCcNoWgMac) == 0;
+  n_rows &= ~(kCcNoSpan | kCcNoWgMac);
   PktCtx c;
   const KeyRow* row;
   constexpr uint32_t kBudget = IMG - kScratchBytes;  // packet images (9728 B at 10 KiB)
-  CcPool pool{false, smem, w * IMG, (uint32_t*)(wsm + kBudget + 32u * (uint32_t)p), kt};
+  CcPool pool{false, smem, w * IMG, (uint32_t*)(wsm + kBudget + 32u * (uint32_t)p), kt, kWg ? cc_role<OPEN>(tb, w, W) : w,
+              wgm};
   if (LIST) {  // the octet region's entries
     n = kPktsPerTile * __builtin_amdgcn_readfirstlane(reg[0]);
     n_dev = nullptr;
@@ -958,10 +1078,19 @@ __device__ __forceinline__ void chacha_tile(uint32_t tb, uint32_t tid, const Key
                                        hpm);
       wave_sync();
     }
+    // the barriers of ChaChaPolicy::seal / open, and this wave's role in the MAC phase
     if (j == 0) pool.rec[0] = 0;
     __syncthreads();
+    if (kWg && OPEN && wgm) {
+      if (pool.role >= W - 2) cc_wg_mac<true, IMG, W>(smem, pool.role - (W - 2), tid);
+      __syncthreads();
+    }
     cc_pool_run<SINGLE, IMG, W, OPEN && kR1, Sp>(pool, tid);
     __syncthreads();
+    if (kWg && !OPEN && wgm) {
+      if (pool.role >= W - 2) cc_wg_mac<false, IMG, W>(smem, pool.role - (W - 2), tid);
+      __syncthreads();
+    }
     return;
   }
   MQ_STAMP(tile_id, 0);
@@ -999,8 +1128,8 @@ __device__ __forceinline__ void chacha_tile(uint32_t tb, uint32_t tid, const Key
     sp.base = wsm;
     MQ_STAMP(tile_id, 1);
     const uint32_t pkt = pl.slot * 16u + pl.head();
-    if (OPEN) ChaChaPolicy::open<kLanesPerPkt, true, SINGLE, IMG, W, kR1>(sp, pkt, c, row, j, false, stg, pool);
-    else ChaChaPolicy::seal<SINGLE, IMG, W, kR1>(sp, pkt, c, row, j, stg, pool);
+    if (OPEN) ChaChaPolicy::open<kLanesPerPkt, true, SINGLE, IMG, W, kR1, kWg>(sp, pkt, c, row, j, false, stg, pool);
+    else ChaChaPolicy::seal<SINGLE, IMG, W, kR1, kWg>(sp, pkt, c, row, j, stg, pool);
     MQ_STAMP(tile_id, 6);
     wave_sync();
     // a packet that failed to open is never stored: such a tile goes back packet by packet
@@ -1010,8 +1139,8 @@ __device__ __forceinline__ void chacha_tile(uint32_t tb, uint32_t tid, const Key
   } else {
     GlobalSpace sp{arena, arena_len};
     NoStager stg;
-    if (OPEN) ChaChaPolicy::open<kLanesPerPkt, true, SINGLE, IMG, W, kR1>(sp, off, c, row, j, true, stg, pool);
-    else ChaChaPolicy::seal<SINGLE, IMG, W, kR1>(sp, off, c, row, j, stg, pool);
+    if (OPEN) ChaChaPolicy::open<kLanesPerPkt, true, SINGLE, IMG, W, kR1, kWg>(sp, off, c, row, j, true, stg, pool);
+    else ChaChaPolicy::seal<SINGLE, IMG, W, kR1, kWg>(sp, off, c, row, j, stg, pool);
   }
   tile_status<OPEN>(c, j, status, pn_out);
 }
@@ -1255,7 +1384,7 @@ __device__ __forceinline__ void chacha_protect_tile(uint32_t tb, const KeyRow* _
   uint8_t* wsm = smem + w * kLdsBytes;
   const int lane = threadIdx.x & (kWave - 1), p = lane / kLanesPerPkt, j = lane % kLanesPerPkt;
   const uint32_t tile_id = tb * W + w;
-  CcPool pool{false, smem, w * kLdsBytes, (uint32_t*)(wsm + kDataBudget + 32u * (uint32_t)p), kt};
+  CcPool pool{false, smem, w * kLdsBytes, (uint32_t*)(wsm + kDataBudget + 32u * (uint32_t)p), kt, w, false};
   const uint32_t tile0 = tile_id * kPktsPerTile;
   if (tile0 >= n) {  // a wave past the batch in a live workgroup joins the barriers and the pool
     if (j == 0) pool.rec[0] = 0;
@@ -1460,7 +1589,9 @@ hipError_t mq_launch_chacha(bool open, const KeyRow* kt, uint32_t n_rows, uint8_
   const KeyRow* kl = one ? kt + single_row : kt;
   // MQ_CC_SPAN=0 (diagnostic, mq_opts.h: tests run both copies on one batch): no span tiles in the
   // octet-tile kernels (chacha_tile reads the bit off n_rows)
-  const uint32_t nr = mq::opt(mq::Opt::CcSpan) == 0 ? n_rows | kCcNoSpan : n_rows;
+  // MQ_CC_WGMAC=0 (likewise): the per-wave MAC in the kernels with the workgroup MAC phase
+  const uint32_t nr = n_rows | (mq::opt(mq::Opt::CcSpan) == 0 ? kCcNoSpan : 0u) |
+                      (mq::opt(mq::Opt::CcWgMac) == 0 ? kCcNoWgMac : 0u);
   if (index && persistent) {
     const uint32_t per = (uint32_t)(cus > 0 ? cus : 256) * 4u, grid = blocks < per ? blocks : per;
     if (open)

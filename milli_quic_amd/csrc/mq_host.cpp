@@ -32,7 +32,7 @@ namespace {
 const char* const kOptNames[(int)mq::Opt::Count] = {
     "MQ_CC_NARROW", "MQ_CC_LONG",  "MQ_CC_LIST",           "MQ_HP_FORK", "MQ_AES_SEG",
     "MQ_PROTECT_FUSED", "MQ_RESIDENT", "MQ_RESIDENT_TIMEOUT_US", "MQ_RECV_SEG", "MQ_AES_HOT_SEG", "MQ_AES_NARROW",
-    "MQ_CC_SPAN"};
+    "MQ_CC_SPAN", "MQ_CC_WGMAC"};
 std::atomic<long> g_opts[(int)mq::Opt::Count];
 std::once_flag g_opts_once;
 void opts_init() {  // once: the environment's values (shell-driven diagnostics keep working)

@@ -24,6 +24,7 @@ enum class Opt : int {
   AesHotSeg,          // MQ_AES_HOT_SEG: 0 runs a partition's hot AES segment on the tile kernel, not the slice kernel
   AesNarrow,          // MQ_AES_NARROW: 0 / 1 / 2 forces 8 / 4 / 2 lanes per packet in the single-key AES kernels
   CcSpan,             // MQ_CC_SPAN: 0 never stages / stores a ChaCha20 octet tile of back-to-back packets as one span
+  CcWgMac,            // MQ_CC_WGMAC: 0 keeps the per-wave Poly1305 in the flat ChaCha20 octet kernels (no workgroup MAC phase)
   Count
 };
 
