@@ -58,8 +58,12 @@ struct OtkRegs {
 // r^(G-j), then the group sum. Every lane of the group returns the same tag.
 // The edge steps of the octet form (kEdge below: the lean stretch up to the last whole block, the
 // general absorb's single byte count) are not taken by the narrow lane groups G < 8: their batches
-// (64- and 256-B packets) measured 0.6 % slower with them (profiles/r09_ab_len_sweep_all_groups.txt).
-template <int G, class S, class K>
+// (64- and 256-B packets) measured 0.6 % slower with them (profiles/r09_ab_len_sweep_all_groups.txt),
+// and at G = 4 in the workgroup MAC phase they gained nothing beyond the spread (profiles/r12_ab_b_variants.txt).
+// PAIR: the lean stretch takes its steps two at a time, ((acc + m_k) R + m_k+1) R as
+// (acc + m_k) R^2 + m_k+1 R with one reduction (p26_mul2), then at most one single step. On for
+// cc_wg_mac only: the other instantiations have no registers to spare for R^2.
+template <int G, bool PAIR = false, class S, class K>
 __device__ __forceinline__ void poly_tag(const S& sp, typename S::off_t pkt, typename S::off_t pay, uint32_t aad_len,
                                          uint32_t ct_len, const K& otk, int j, bool act, uint32_t (&tag)[4]) {
   typedef Grp<G> Gp;
@@ -170,6 +174,26 @@ __device__ __forceinline__ void poly_tag(const S& sp, typename S::off_t pkt, typ
         typename S::off_t a = b.src & ~(typename S::off_t)3;
         uint32_t sel = sel_pay;
         pin(sel);  // keep the selector in a register (hipcc rematerialised it every step)
+        if (PAIR && khi - k >= 2) {  // wave-uniform, so r^(2G) is paid only where a pair runs
+          // two steps per reduction. The loads are the single steps' very sequence (each step fetches
+          // the next one's block at a += 16 G), so the look-ahead bound does not move: below
+          // pay + 16 T + 20, inside the workgroup's allocation (cc_wg_mac). klo and khi are
+          // wave-uniform, so this loop is too.
+          P26 r2G = rG;
+          p26_mul(r2G, mG);
+          const P26m mG2 = p26_mult(r2G);
+          for (; k + 1 < khi; k += 2) {
+            const P26 x = p26_from_words(m[0], m[1], m[2], m[3], 1u);
+#pragma unroll
+            for (int l = 0; l < 5; ++l) acc.l[l] += x.l[l];
+            a += 16 * G;
+            load_words_sel<4>(sp, a, sel, m);
+            const P26 y = p26_from_words(m[0], m[1], m[2], m[3], 1u);
+            a += 16 * G;
+            load_words_sel<4>(sp, a, sel, m);
+            p26_mul2(acc, mG2, y, mG);
+          }
+        }
         for (; k < khi; ++k) {
           const P26 x = p26_from_words(m[0], m[1], m[2], m[3], 1u);
 #pragma unroll
@@ -344,7 +368,9 @@ template <> struct PoolSpace<LdsSpaceRaw> { typedef LdsSpaceRaw type; };
 // record and, for a packet that fails, clears the record's pooled blocks, so nothing of it is
 // decrypted. The lean stretch's look-ahead reads (poly_tag) end in the next image or in a wave's
 // scratch: inside the workgroup's allocation.
-template <bool OPEN, uint32_t IMG, uint32_t W>
+// PAIR: poly_tag's pair loop. Off in the multi-key open kernel alone, which measured 0.7 % slower with
+// it (124 VGPRs for 120; profiles/r12_ab_bk1024_pair_everywhere.txt).
+template <bool OPEN, uint32_t IMG, uint32_t W, bool PAIR = true>
 __device__ __forceinline__ void cc_wg_mac(uint8_t* wg, uint32_t m, uint32_t tid) {
   constexpr int G = 4;
   static_assert(kPktsPerTile * W == 2 * (kWave / G), "two MAC waves of 16 packets");
@@ -357,7 +383,8 @@ __device__ __forceinline__ void cc_wg_mac(uint8_t* wg, uint32_t m, uint32_t tid)
   const uint32_t pay = act ? r1 & 0x1ffffu : 0u, P = act ? r1 >> 17 : 0u;
   LdsSpace sp{wg};
   uint32_t tag[4];
-  poly_tag<G>(sp, pay - aad_len, pay, aad_len, P, OtkLds{rec + 8 * kPktsPerTile}, j, act, tag);  // the key: 8 records on
+  // the key: 8 records on
+  poly_tag<G, PAIR>(sp, pay - aad_len, pay, aad_len, P, OtkLds{rec + 8 * kPktsPerTile}, j, act, tag);
   if (OPEN) {
     uint32_t got[4];
     load_words<4>(sp, pay + P, got);
@@ -675,7 +702,7 @@ struct ChaChaPolicy {
       if (pool.mac) {  // nothing to hand over
         if (j == 0) pool.rec[0] = 0;
         __syncthreads();
-        if (pool.role >= W - 2) cc_wg_mac<true, IMG, W>(pool.wg, pool.role - (W - 2), threadIdx.x);
+        if (pool.role >= W - 2) cc_wg_mac<true, IMG, W, SINGLE>(pool.wg, pool.role - (W - 2), threadIdx.x);
         __syncthreads();
       }
     }
@@ -752,7 +779,7 @@ struct ChaChaPolicy {
       if (wgm) {
         if (j == 0) pool_record();
         __syncthreads();  // every wave's records, keys and unmasked headers
-        if (pool.role >= W - 2) cc_wg_mac<true, IMG, W>(pool.wg, pool.role - (W - 2), threadIdx.x);
+        if (pool.role >= W - 2) cc_wg_mac<true, IMG, W, SINGLE>(pool.wg, pool.role - (W - 2), threadIdx.x);
         __syncthreads();  // every verdict; every MAC has read its ciphertext
         if (handed && c.act) diff = pool.rec[2];
       }
@@ -1082,7 +1109,7 @@ __device__ __forceinline__ void chacha_tile(uint32_t tb, uint32_t tid, const Key
     if (j == 0) pool.rec[0] = 0;
     __syncthreads();
     if (kWg && OPEN && wgm) {
-      if (pool.role >= W - 2) cc_wg_mac<true, IMG, W>(smem, pool.role - (W - 2), tid);
+      if (pool.role >= W - 2) cc_wg_mac<true, IMG, W, SINGLE>(smem, pool.role - (W - 2), tid);
       __syncthreads();
     }
     cc_pool_run<SINGLE, IMG, W, OPEN && kR1, Sp>(pool, tid);

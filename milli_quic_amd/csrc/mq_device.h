@@ -18,6 +18,7 @@
 
 #include "../../include/mq_aead.h"
 #include "mq_poly_sched.h"
+#include "mq_poly26.h"
 
 namespace mq {
 
@@ -569,80 +570,6 @@ __device__ __forceinline__ void chacha20_block(const uint32_t (&key)[8], uint32_
   out[12] = x12 + ctr; out[13] = x13 + n0; out[14] = x14 + n1; out[15] = x15 + n2;
 }
 
-// ------------------------------------------------------------------------------------------
-// Poly1305 arithmetic mod 2^130-5 in radix 2^26 (5 limbs), general multiplier (r, r^2..r^4).
-struct P26 { uint32_t l[5]; };
-struct P26m { uint32_t r[5], s[4]; };  // multiplier with s[i] = 5 * r[i+1]
-
-__device__ __forceinline__ P26m p26_mult(const P26& r) {
-  P26m m;
-#pragma unroll
-  for (int i = 0; i < 5; ++i) m.r[i] = r.l[i];
-#pragma unroll
-  for (int i = 0; i < 4; ++i) m.s[i] = r.l[i + 1] * 5u;
-  return m;
-}
-
-__device__ __forceinline__ P26 p26_from_words(uint32_t t0, uint32_t t1, uint32_t t2, uint32_t t3,
-                                              uint32_t hibit) {
-  P26 h;
-  h.l[0] = t0 & 0x3ffffff;
-  h.l[1] = ((t0 >> 26) | (t1 << 6)) & 0x3ffffff;
-  h.l[2] = ((t1 >> 20) | (t2 << 12)) & 0x3ffffff;
-  h.l[3] = ((t2 >> 14) | (t3 << 18)) & 0x3ffffff;
-  h.l[4] = (t3 >> 8) | (hibit << 24);
-  return h;
-}
-
-// h = h * m (mod 2^130 - 5), partially reduced (limbs < 2^26, l[1] < 2^26 + 2^9). Inputs: limbs
-// < 2^27 (a product plus one absorbed block), multiplier limbs < 2^26 (s < 2^28.4), so every
-// column sum stays below 2^58 and each carry (d >> 26) below 2^32, so the top carry is a 32-bit
-// operand of the x5 fold.
-__device__ __forceinline__ void p26_mul(P26& h, const P26m& m) {
-  const uint32_t h0 = h.l[0], h1 = h.l[1], h2 = h.l[2], h3 = h.l[3], h4 = h.l[4];
-  const uint64_t d0 = (uint64_t)h0 * m.r[0] + (uint64_t)h1 * m.s[3] + (uint64_t)h2 * m.s[2] + (uint64_t)h3 * m.s[1] + (uint64_t)h4 * m.s[0];
-  const uint64_t d1 = (d0 >> 26) + (uint64_t)h0 * m.r[1] + (uint64_t)h1 * m.r[0] + (uint64_t)h2 * m.s[3] + (uint64_t)h3 * m.s[2] + (uint64_t)h4 * m.s[1];
-  const uint64_t d2 = (d1 >> 26) + (uint64_t)h0 * m.r[2] + (uint64_t)h1 * m.r[1] + (uint64_t)h2 * m.r[0] + (uint64_t)h3 * m.s[3] + (uint64_t)h4 * m.s[2];
-  const uint64_t d3 = (d2 >> 26) + (uint64_t)h0 * m.r[3] + (uint64_t)h1 * m.r[2] + (uint64_t)h2 * m.r[1] + (uint64_t)h3 * m.r[0] + (uint64_t)h4 * m.s[3];
-  const uint64_t d4 = (d3 >> 26) + (uint64_t)h0 * m.r[4] + (uint64_t)h1 * m.r[3] + (uint64_t)h2 * m.r[2] + (uint64_t)h3 * m.r[1] + (uint64_t)h4 * m.r[0];
-  const uint32_t c4 = (uint32_t)(d4 >> 26);
-  const uint64_t t = (uint64_t)((uint32_t)d0 & 0x3ffffff) + (uint64_t)c4 * 5u;
-  h.l[0] = (uint32_t)t & 0x3ffffff;
-  h.l[1] = ((uint32_t)d1 & 0x3ffffff) + (uint32_t)(t >> 26);
-  h.l[2] = (uint32_t)d2 & 0x3ffffff;
-  h.l[3] = (uint32_t)d3 & 0x3ffffff;
-  h.l[4] = (uint32_t)d4 & 0x3ffffff;
-}
-
-// Full reduction mod p and tag = (h + s) mod 2^128, as 4 LE words.
-__device__ __forceinline__ void p26_finish(P26 h, const uint32_t (&s)[4], uint32_t (&tag)[4]) {
-  uint32_t c;
-  c = h.l[0] >> 26; h.l[0] &= 0x3ffffff; h.l[1] += c;
-  c = h.l[1] >> 26; h.l[1] &= 0x3ffffff; h.l[2] += c;
-  c = h.l[2] >> 26; h.l[2] &= 0x3ffffff; h.l[3] += c;
-  c = h.l[3] >> 26; h.l[3] &= 0x3ffffff; h.l[4] += c;
-  c = h.l[4] >> 26; h.l[4] &= 0x3ffffff; h.l[0] += c * 5;
-  c = h.l[0] >> 26; h.l[0] &= 0x3ffffff; h.l[1] += c;
-  c = h.l[1] >> 26; h.l[1] &= 0x3ffffff; h.l[2] += c;
-  uint32_t g0, g1, g2, g3, g4;
-  g0 = h.l[0] + 5; c = g0 >> 26; g0 &= 0x3ffffff;
-  g1 = h.l[1] + c; c = g1 >> 26; g1 &= 0x3ffffff;
-  g2 = h.l[2] + c; c = g2 >> 26; g2 &= 0x3ffffff;
-  g3 = h.l[3] + c; c = g3 >> 26; g3 &= 0x3ffffff;
-  g4 = h.l[4] + c - (1u << 26);
-  bool use_g = (g4 >> 31) == 0;
-  uint32_t f0 = use_g ? g0 : h.l[0], f1 = use_g ? g1 : h.l[1], f2 = use_g ? g2 : h.l[2];
-  uint32_t f3 = use_g ? g3 : h.l[3], f4 = use_g ? g4 : h.l[4];
-  uint32_t w0 = f0 | (f1 << 26), w1 = (f1 >> 6) | (f2 << 20), w2 = (f2 >> 12) | (f3 << 14),
-           w3 = (f3 >> 18) | (f4 << 8);
-  uint64_t t = (uint64_t)w0 + s[0];
-  tag[0] = (uint32_t)t;
-  t = (uint64_t)w1 + s[1] + (t >> 32);
-  tag[1] = (uint32_t)t;
-  t = (uint64_t)w2 + s[2] + (t >> 32);
-  tag[2] = (uint32_t)t;
-  t = (uint64_t)w3 + s[3] + (t >> 32);
-  tag[3] = (uint32_t)t;
-}
+// Poly1305 arithmetic mod 2^130-5 in radix 2^26 (P26, p26_mul, p26_mul2, p26_finish): mq_poly26.h.
 
 }  // namespace mq
