@@ -96,26 +96,29 @@ MQ_HD void p26_finish(P26 h, const uint32_t (&s)[4], uint32_t (&tag)[4]) {
   c = h.l[2] >> 26; h.l[2] &= 0x3ffffff; h.l[3] += c;
   c = h.l[3] >> 26; h.l[3] &= 0x3ffffff; h.l[4] += c;
   c = h.l[4] >> 26; h.l[4] &= 0x3ffffff; h.l[0] += c * 5;
-  c = h.l[0] >> 26; h.l[0] &= 0x3ffffff; h.l[1] += c;
-  c = h.l[1] >> 26; h.l[1] &= 0x3ffffff; h.l[2] += c;
+  // h < 2 p now, limbs 1 .. 4 below 2^26 and limb 0 a few fives above it at most. g = h + 5 in
+  // normalised limbs (g4 may reach 2^26) carries whatever the fold left; h itself is not carried on:
+  // a lane sum c 2^130 + (2^128 - 5 c) has limbs 1 .. 3 all ones, its fold ripples up to limb 4, and
+  // a chain on h that stops early packs a limb of 2^26 into the words. Both results come from g:
+  // h >= p: (h - p) = g - 2^130, which is g mod 2^128; h < p: h = g - 5, taken off in the tag's sum
+  // as + (2^128 - 5).
   uint32_t g0, g1, g2, g3, g4;
   g0 = h.l[0] + 5; c = g0 >> 26; g0 &= 0x3ffffff;
   g1 = h.l[1] + c; c = g1 >> 26; g1 &= 0x3ffffff;
   g2 = h.l[2] + c; c = g2 >> 26; g2 &= 0x3ffffff;
   g3 = h.l[3] + c; c = g3 >> 26; g3 &= 0x3ffffff;
-  g4 = h.l[4] + c - (1u << 26);
-  bool use_g = (g4 >> 31) == 0;
-  uint32_t f0 = use_g ? g0 : h.l[0], f1 = use_g ? g1 : h.l[1], f2 = use_g ? g2 : h.l[2];
-  uint32_t f3 = use_g ? g3 : h.l[3], f4 = use_g ? g4 : h.l[4];
-  uint32_t w0 = f0 | (f1 << 26), w1 = (f1 >> 6) | (f2 << 20), w2 = (f2 >> 12) | (f3 << 14),
-           w3 = (f3 >> 18) | (f4 << 8);
-  uint64_t t = (uint64_t)w0 + s[0];
+  g4 = h.l[4] + c;
+  bool use_g = (g4 >> 26) != 0;
+  const uint32_t k = use_g ? 0u : 0xffffffffu;  // the words of 2^128 - 5: k - 4, k, k, k
+  uint32_t w0 = g0 | (g1 << 26), w1 = (g1 >> 6) | (g2 << 20), w2 = (g2 >> 12) | (g3 << 14),
+           w3 = (g3 >> 18) | (g4 << 8);
+  uint64_t t = (uint64_t)w0 + s[0] + (k & 0xfffffffbu);
   tag[0] = (uint32_t)t;
-  t = (uint64_t)w1 + s[1] + (t >> 32);
+  t = (uint64_t)w1 + s[1] + k + (t >> 32);
   tag[1] = (uint32_t)t;
-  t = (uint64_t)w2 + s[2] + (t >> 32);
+  t = (uint64_t)w2 + s[2] + k + (t >> 32);
   tag[2] = (uint32_t)t;
-  t = (uint64_t)w3 + s[3] + (t >> 32);
+  t = (uint64_t)w3 + s[3] + k + (t >> 32);
   tag[3] = (uint32_t)t;
 }
 

@@ -24,7 +24,7 @@ def test_poly_pair_asan_ubsan(tmp_path):
         pytest.skip("no g++")
     exe = tmp_path / "test_poly_pair"
     subprocess.run([cxx, "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                    "-fno-omit-frame-pointer", "-Wall", "-Wextra", "-Werror",
+                    "-fno-omit-frame-pointer", "-Wall", "-Wextra", "-Werror", "-I", os.path.join(ROOT, "milli_quic_amd", "csrc"),
                     os.path.join(ROOT, "tests", "csrc", "test_poly_pair.cpp"), "-o", str(exe)], check=True)
     env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=1",
                UBSAN_OPTIONS="halt_on_error=1:print_stacktrace=1")
