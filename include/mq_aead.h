@@ -230,6 +230,15 @@ int mq_debug_chacha_flat_kind(uint64_t arena_len, uint32_t n, uint32_t suite_hin
 /* The same for a flat single-key AES-128-GCM batch: its lanes per packet — 2 (tiles of 32 short
  * packets), 4 (16 packets) or 8 (octet tiles); -1 for n = 0. */
 int mq_debug_aes_flat_kind(uint64_t arena_len, uint32_t n, uint32_t suite_hint);
+/* The path mq_batch_seal / mq_batch_open take for n packets with the AES-128-GCM hint, a workspace and
+ * a key table of n_rows rows (the MIXED hint takes the same path over several rows), as kind |
+ * lanes << 8; -1 for n = 0 or n_rows = 0. kind: 0 flat single-key kernels, 1 flat multi-key kernel
+ * (more than 2^30 packets; also every batch over several rows without a workspace), 2 partition with
+ * the hot key's segment on a single-key kernel beside the multi-key kernel, 3 partition with the
+ * whole list on the key-segmented single-key kernels. lanes: lanes per packet of the single-key tiles
+ * (kind 1: the multi-key kernel's 8); 0 for kind 0 without MQ_AES_NARROW, where the bytes per packet
+ * decide (mq_debug_aes_flat_kind). The diagnostic switches in force are taken into account. */
+int mq_debug_aes_list_kind(uint32_t n, uint32_t n_rows);
 
 /* ---- CryptoProvider::aead / Aead (per packet, host buffers; runs the HIP kernels) ----------- */
 /* provider.aead(key): key_len must equal KEY_LEN of the suite (rustcrypto.rs:234-236, 267-269) */

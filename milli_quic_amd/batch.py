@@ -227,3 +227,18 @@ def aes_flat_kind(arena_len, n, suite_hint):
     """Lanes per packet of the flat single-key AES-128-GCM kernels a batch would run
     (mq_debug_aes_flat_kind): 2 (32 packets per wave), 4 (16) or 8 (octet tiles)."""
     return _lib.load().mq_debug_aes_flat_kind(int(arena_len), int(n), int(suite_hint))
+
+
+AES_FLAT_SINGLE, AES_FLAT_MULTI, AES_PARTITION_HOT, AES_KEY_SEGMENTS = range(4)
+
+
+def aes_list_kind(n, n_rows):
+    """(kind, lanes) of the path a batch of n packets with the AES-128-GCM hint and a workspace takes
+    over a key table of n_rows rows (mq_debug_aes_list_kind; the MIXED hint takes the same path over
+    several rows): AES_FLAT_SINGLE, AES_FLAT_MULTI, AES_PARTITION_HOT (the hot key's segment split
+    off the partition list) or AES_KEY_SEGMENTS, and the lanes per packet of its single-key tiles
+    (0: a flat single-key batch without MQ_AES_NARROW, see aes_flat_kind)."""
+    v = _lib.load().mq_debug_aes_list_kind(int(n), int(n_rows))
+    if v < 0:
+        raise crypto.InvalidArgument("n and n_rows must be positive")
+    return v & 0xFF, v >> 8

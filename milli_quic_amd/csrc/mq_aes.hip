@@ -1012,6 +1012,7 @@ static int aes_lanes(bool flat, uint64_t bpp) {
   return bpp <= kAesNarrow2MaxBpp ? 2 : 4;
 }
 int mq_aes_flat_lanes(uint64_t bpp) { return aes_lanes(true, bpp); }
+int mq_aes_list_lanes() { return aes_lanes(false, 0); }
 using AesSealK = void (*)(const KeyRow*, uint32_t, uint8_t*, uint64_t, const mq_pkt_desc*, uint32_t, const uint32_t*,
                           const uint32_t*, const uint32_t*, uint8_t*, uint32_t*);
 using AesOpenK = void (*)(const KeyRow*, uint32_t, uint8_t*, uint64_t, const mq_pkt_desc*, uint32_t, const uint32_t*,

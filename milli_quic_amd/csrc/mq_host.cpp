@@ -26,6 +26,8 @@ using mq::KeyRow;
 
 int mq_chacha_flat_kind(uint64_t bpp);  // mq_chacha.hip
 int mq_aes_flat_lanes(uint64_t bpp);    // mq_aes.hip
+int mq_aes_list_lanes();                // mq_aes.hip
+bool mq_partition_keyed(uint32_t n, uint32_t n_rows);  // mq_partition.hip
 
 // ---- diagnostic switches (mq_opts.h) ---------------------------------------------------------
 namespace {
@@ -77,6 +79,34 @@ extern "C" int mq_debug_aes_flat_kind(uint64_t arena_len, uint32_t n, uint32_t s
   const uint64_t len_hint = suite_hint >> 16;
   if (n == 0) return -1;
   return mq_aes_flat_lanes(len_hint ? len_hint : (arena_len + n - 1) / n);
+}
+
+// The path a batch's AES-128-GCM packets take, decided here and nowhere else: batch() launches what
+// this returns, and mq_debug_aes_list_kind reports it.
+//   flat (the AES-128-GCM hint over a one-row table, without a workspace, or beyond the partition's
+//   2^30 packets): the single-key kernels for one row, else the multi-key kernel;
+//   otherwise the partition, whose list 0 runs either as the hot key's segment on a single-key
+//   kernel beside the multi-key kernel, or whole on the key-segmented single-key kernels: keys with
+//   many packets each (on average >= kSegPackets per row) in the keyed layout. MQ_AES_SEG
+//   (diagnostic): 0 = never, 1 = whenever the layout is keyed.
+enum AesListKind { kAesFlatSingle = 0, kAesFlatMulti = 1, kAesPartitionHot = 2, kAesKeySegments = 3 };
+static AesListKind aes_list_kind(uint32_t suite_hint, uint32_t n, uint32_t n_rows, bool has_ws) {
+  if (suite_hint == MQ_SUITE_AES128GCM && (n_rows == 1 || !has_ws || n > (1u << 30)))
+    return n_rows == 1 ? kAesFlatSingle : kAesFlatMulti;
+  constexpr uint32_t kSegPackets = 512;
+  const long seg_opt = mq::opt(mq::Opt::AesSeg);
+  const bool seg = seg_opt != 0 && (seg_opt == 1 || (uint64_t)n >= (uint64_t)kSegPackets * n_rows) &&
+                   mq_partition_keyed(n, n_rows);
+  return seg ? kAesKeySegments : kAesPartitionHot;
+}
+
+extern "C" int mq_debug_aes_list_kind(uint32_t n, uint32_t n_rows) {
+  if (n == 0 || n_rows == 0) return -1;
+  const AesListKind kind = aes_list_kind(MQ_SUITE_AES128GCM, n, n_rows, true);
+  int lanes = mq_aes_list_lanes();                                                   // segments of a partition list
+  if (kind == kAesFlatSingle) lanes = mq::opt(mq::Opt::AesNarrow) >= 0 ? mq_aes_flat_lanes(0) : 0;  // else by bytes per packet
+  if (kind == kAesFlatMulti) lanes = 8;
+  return (int)kind | lanes << 8;
 }
 
 extern "C" long mq_debug_option_get(const char* name) {
@@ -1025,7 +1055,7 @@ static int batch(bool open, const mq_keytable* kt, uint8_t* arena, uint64_t aren
   if (suite_hint == MQ_SUITE_CHACHA20) {
     e = mq_launch_chacha(open, kt->dev, kt->rows, arena, arena_len, desc, n, nullptr, nullptr, status, pn_out, hpm, true,
                          s, cus, nullptr, -1, false, nullptr, bpp);
-  } else if (suite_hint == MQ_SUITE_AES128GCM && (kt->rows == 1 || !ws || n > (1u << 30))) {
+  } else if (suite_hint == MQ_SUITE_AES128GCM && aes_list_kind(suite_hint, n, kt->rows, ws != nullptr) <= kAesFlatMulti) {
     e = mq_launch_aes(open, kt->dev, kt->rows, arena, arena_len, desc, n, nullptr, nullptr, nullptr, status, pn_out,
                       hpm, true, s, s, cus, nullptr, sched_slot(kt->device, s), nullptr, bpp);
   } else if (suite_hint == MQ_SUITE_MIXED || suite_hint == MQ_SUITE_AES128GCM) {
@@ -1066,14 +1096,11 @@ static int batch(bool open, const mq_keytable* kt, uint8_t* arena, uint64_t aren
     // 1.346 -> 1.562 ms seal), because its 40-KiB workgroups take CUs that the persistent AES
     // grids (one 152-KiB workgroup per CU) then wait for. Side streams are per (device, caller
     // stream): mq_runtime.h.
-    // Keys with many packets each (on average >= kSegPackets per row, keyed layout): the
-    // key-segmented single-key kernels run list 0 whole, no fork (mq_aes.hip aes_seg_tiles)
-    constexpr uint32_t kSegPackets = 512;
-    const long seg_opt = mq::opt(mq::Opt::AesSeg);  // diagnostic: 0 = never, 1 = whenever keyed
-    const bool seg_force = seg_opt == 1;
-    const uint32_t* rowseg = seg_opt == 0 || (!seg_force && (uint64_t)n < (uint64_t)kSegPackets * kt->rows)
-                                 ? nullptr
-                                 : mq_partition_rowseg(n, kt->rows, counts);
+    // Keys with many packets each (aes_list_kind): the key-segmented single-key kernels run list 0
+    // whole, no fork (mq_aes.hip aes_seg_tiles)
+    const uint32_t* rowseg = aes_list_kind(suite_hint, n, kt->rows, true) == kAesKeySegments
+                                 ? mq_partition_rowseg(n, kt->rows, counts)
+                                 : nullptr;
     auto fork = fork_enabled() && !rowseg ? side_streams().fork(kt->device, s, 1) : mq::SideStreams<HipBackend>::Fork();
     // list 1 stays on s: after the hot segment on its side stream instead it cost E 2 % (the slice
     // kernel) to 10 % (the tile kernel) (profiles/r06r_ab_e_list1_after_hot_rejected.txt)

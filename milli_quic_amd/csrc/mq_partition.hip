@@ -646,6 +646,7 @@ static size_t part_align(size_t b) { return (b + 255) & ~(size_t)255; }
 // The per-row segments of a keyed partition (rowseg, 2 words per row, keyed_ws), or null when
 // mq_launch_partition(n, n_rows) does not lay the list out keyed. counts: the partition's meta (as
 // passed to mq_launch_partition).
+bool mq_partition_keyed(uint32_t n, uint32_t n_rows) { return keyed_layout(n, n_rows); }
 const uint32_t* mq_partition_rowseg(uint32_t n, uint32_t n_rows, const uint32_t* counts) {
   if (!keyed_layout(n, n_rows)) return nullptr;
   return keyed_ws((uint32_t*)((uint8_t*)counts + part_align(sizeof(uint32_t) * kMetaWords)), n_rows).rowseg;

@@ -125,6 +125,19 @@ def test_flat_aes_kernel_choice(mqlib):
     assert kind(0, 0, A) == -1
 
 
+def test_aes_list_kind(mqlib):
+    # the decision itself: segments by themselves from 512 packets per row on, never without the
+    # keyed layout (4096 rows need ~44 000 packets), flat beyond 2^30 packets
+    from milli_quic_amd import batch
+    kind = batch.aes_list_kind
+    assert kind(1000, 1) == (batch.AES_FLAT_SINGLE, 0)
+    assert kind(3 * 512 - 1, 3)[0] == batch.AES_PARTITION_HOT and kind(3 * 512, 3) == (batch.AES_KEY_SEGMENTS, 4)
+    assert kind((1 << 30) + 1, 3) == (batch.AES_FLAT_MULTI, 8)
+    with _lib.option("MQ_AES_SEG", 1):
+        assert kind(8000, 4096)[0] == batch.AES_PARTITION_HOT and kind(46000, 4096)[0] == batch.AES_KEY_SEGMENTS
+    assert mqlib.mq_debug_aes_list_kind(0, 3) == -1 and mqlib.mq_debug_aes_list_kind(5, 0) == -1
+
+
 def test_debug_options(mqlib):
     # diagnostic switches: set, read back, unset; unknown names refused; a batch never reads the
     # environment on its hot path (mq_opts.h)
