@@ -219,7 +219,7 @@ const char* mq_status_str(int status);
  * MQ_PROTECT_FUSED, MQ_RESIDENT, MQ_RESIDENT_TIMEOUT_US, MQ_RECV_SEG, MQ_AES_HOT_SEG, MQ_AES_NARROW,
  * MQ_CC_SPAN, MQ_CC_WGMAC. Each starts from the environment variable of that name (read once, at the first use of any
  * switch); value < 0 unsets it (the product behaviour). MQ_OK, or MQ_ERR_INVALID_ARG for an unknown name. A batch reads each
- * switch once per call. */
+ * switch once per mq_batch_* call. */
 int mq_debug_option(const char* name, long value);
 /* The switch's value: -1 unset, -2 unknown name. */
 long mq_debug_option_get(const char* name);

@@ -31,7 +31,7 @@
 // keystream again, so every failed packet ends byte-identical to its input (recv.rs:416-421).
 #include "mq_aes.h"
 #include "mq_tile.h"
-#include "mq_opts.h"
+#include "mq_launch.h"
 
 #include <cstdlib>
 
@@ -1004,15 +1004,14 @@ constexpr uint64_t kAesNarrowMaxBpp = MQ_AES_NARROW_MAX, kAesNarrow2MaxBpp = MQ_
 // lanes per packet of the single-key tiles: MQ_AES_NARROW 0 -> 8, 1 -> 4, 2 -> 2; unset: flat
 // batches by their bytes per packet, partition segments (mixed lengths: config E 2.42 ms with 4,
 // 2.47 with 2, r06l) 4
-static int aes_lanes(bool flat, uint64_t bpp) {
-  const long f = opt(Opt::AesNarrow);
+static int aes_lanes(long f, bool flat, uint64_t bpp) {
   if (f >= 0) return f == 0 ? 8 : f == 2 ? 2 : 4;
   if (!flat) return 4;
   if (bpp == 0 || bpp > kAesNarrowMaxBpp) return 8;
   return bpp <= kAesNarrow2MaxBpp ? 2 : 4;
 }
-int mq_aes_flat_lanes(uint64_t bpp) { return aes_lanes(true, bpp); }
-int mq_aes_list_lanes() { return aes_lanes(false, 0); }
+int mq_aes_flat_lanes(long narrow, uint64_t bpp) { return aes_lanes(narrow, true, bpp); }
+int mq_aes_list_lanes(long narrow) { return aes_lanes(narrow, false, 0); }
 using AesSealK = void (*)(const KeyRow*, uint32_t, uint8_t*, uint64_t, const mq_pkt_desc*, uint32_t, const uint32_t*,
                           const uint32_t*, const uint32_t*, uint8_t*, uint32_t*);
 using AesOpenK = void (*)(const KeyRow*, uint32_t, uint8_t*, uint64_t, const mq_pkt_desc*, uint32_t, const uint32_t*,
@@ -1027,90 +1026,61 @@ static AesOpenK open1_of(int g) { return g == 2 ? mq_aes_open1n2_kernel : g == 4
 static AesSegSealK seals_of(int g) { return g == 2 ? mq_aes_sealsn2_kernel : g == 4 ? mq_aes_sealsn_kernel : mq_aes_seals_kernel; }
 static AesSegOpenK opens_of(int g) { return g == 2 ? mq_aes_opensn2_kernel : g == 4 ? mq_aes_opensn_kernel : mq_aes_opens_kernel; }
 
-hipError_t mq_launch_aes(bool open, const KeyRow* kt, uint32_t n_rows, uint8_t* arena, uint64_t arena_len,
-                         const mq_pkt_desc* desc, uint32_t n, const uint32_t* index, const uint32_t* n_dev,
-                         const uint32_t* hot, uint8_t* status, uint64_t* pn_out, uint2* hpm, bool own_hp,
-                         hipStream_t s, hipStream_t hs, int cus, const uint32_t* rowseg, uint32_t* sched_s,
-                         uint32_t* sched_hs, uint64_t bpp) {
+hipError_t mq_launch_aes(const mq::BatchArgs& b, const mq::TileLaunch& l) {
+  const uint32_t n = l.n, n_rows = b.n_rows;
   const uint32_t tiles = (n + kPktsPerTile - 1) / kPktsPerTile;
   if (tiles == 0) return hipSuccess;
-  const int gflat = aes_lanes(true, bpp);
-  if (n_rows == 1 && !index && !n_dev && !hot && gflat != 8) {
-    const uint32_t waves = aes_waves(true), ppt = 64u / (uint32_t)gflat, blocks = aes_grid((n + ppt - 1) / ppt, waves, cus);
-    if (open && hpm && own_hp) {
-      hipLaunchKernelGGL(mq_aes_open_hp_kernel<true>, dim3((n + 255) / 256), dim3(256), 0, s, kt, n_rows, arena,
-                         arena_len, desc, n, index, n_dev, hpm);
-      const hipError_t e = hipGetLastError();
-      if (e != hipSuccess) return e;
-    }
-    if (open)
-      hipLaunchKernelGGL(open1_of(gflat), dim3(blocks), dim3(64 * waves), 0, s, kt, n_rows, arena, arena_len, desc,
-                         n, index, n_dev, hot, status, pn_out, hpm, sched_s);
+  if (b.open && b.hpm && l.own_hp) {  // !own_hp: mq_launch_mixed_hp covers both suites' lists
+    hipLaunchKernelGGL(mq_aes_open_hp_kernel<true>, dim3((n + 255) / 256), dim3(256), 0, l.s, b.kt, n_rows, b.arena,
+                       b.arena_len, b.desc, n, l.index, l.n_dev, b.hpm);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+  }
+  // One kernel of a seal / open pair on stream st: both take the key table, the arena, the descriptors,
+  // the pair's own arguments (mid), the status and last the stream's schedule slot; the open kernel
+  // pn_out and hpm before the slot.
+  auto launch = [&](auto seal, auto open, dim3 grid, dim3 block, hipStream_t st, uint32_t* sched, auto... mid) {
+    if (b.open)
+      hipLaunchKernelGGL(open, grid, block, 0, st, b.kt, n_rows, b.arena, b.arena_len, b.desc, mid..., b.status, b.pn_out,
+                         b.hpm, sched);
     else
-      hipLaunchKernelGGL(seal1_of(gflat), dim3(blocks), dim3(64 * waves), 0, s, kt, n_rows, arena, arena_len, desc,
-                         n, index, n_dev, hot, status, sched_s);
+      hipLaunchKernelGGL(seal, grid, block, 0, st, b.kt, n_rows, b.arena, b.arena_len, b.desc, mid..., b.status, sched);
+  };
+  const int gflat = aes_lanes(b.sw.aes_narrow, true, b.bpp);
+  if (n_rows == 1 && !l.index && !l.n_dev && !l.hot && gflat != 8) {
+    const uint32_t waves = aes_waves(true), ppt = 64u / (uint32_t)gflat, blocks = aes_grid((n + ppt - 1) / ppt, waves, b.cus);
+    launch(seal1_of(gflat), open1_of(gflat), dim3(blocks), dim3(64 * waves), l.s, l.sched, n, l.index, l.n_dev, l.hot);
     return hipGetLastError();
   }
   // the hot key's segment of a partition list, and the key-segmented kernels' segments, run narrow
   // tiles too, unless MQ_AES_NARROW=0
-  const int ghot = aes_lanes(false, bpp);
-  if (rowseg && index && hot && n_rows > 1 && !own_hp) {
-    const uint32_t blocks = (uint32_t)(cus > 0 ? cus : 256);
-    if (open)
-      hipLaunchKernelGGL(opens_of(ghot), dim3(blocks),
-                         dim3(64 * aes_seg_waves()), 0, s, kt, n_rows, arena, arena_len, desc, index, n_dev, hot,
-                         rowseg, status, pn_out, hpm, sched_s);
-    else
-      hipLaunchKernelGGL(seals_of(ghot), dim3(blocks),
-                         dim3(64 * aes_seg_waves()), 0, s, kt, n_rows, arena, arena_len, desc, index, n_dev, hot,
-                         rowseg, status, sched_s);
+  const int ghot = aes_lanes(b.sw.aes_narrow, false, b.bpp);
+  const dim3 seg_grid((uint32_t)(b.cus > 0 ? b.cus : 256)), seg_block(64 * aes_seg_waves());
+  if (l.rowseg && l.index && l.hot && n_rows > 1 && !l.own_hp) {
+    launch(seals_of(ghot), opens_of(ghot), seg_grid, seg_block, l.s, l.sched, l.index, l.n_dev, l.hot, l.rowseg);
     return hipGetLastError();
   }
-  const uint32_t waves = aes_waves(n_rows == 1), blocks = aes_grid(tiles, waves, cus);
+  const uint32_t waves = aes_waves(n_rows == 1), blocks = aes_grid(tiles, waves, b.cus);
   // a partition list over several rows: the hot key's segment on a single-key kernel first
-  hot = (hot && index && n_rows > 1) ? hot : nullptr;
-  const uint32_t hot_blocks = hot ? aes_grid(tiles, aes_waves(true), cus) : 0u;
-  if (open && hpm && own_hp) {  // !own_hp: mq_launch_mixed_hp covers both suites' lists
-    hipLaunchKernelGGL(mq_aes_open_hp_kernel<true>, dim3((n + 255) / 256), dim3(256), 0, s, kt, n_rows, arena,
-                       arena_len, desc, n, index, n_dev, hpm);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-  }
-  if (!hot) hs = s;
+  const uint32_t* hot = (l.hot && l.index && n_rows > 1) ? l.hot : nullptr;
+  const hipStream_t hs = hot ? l.hs : l.s;
   // the launch's own HP passes run on s: a forked hot kernel would race them
-  if (own_hp && hs != s) return hipErrorInvalidValue;
+  if (l.own_hp && hs != l.s) return hipErrorInvalidValue;
   // two kernels at once on one stream's slot would share its heads
-  if (hot && hs == s) sched_hs = nullptr;
+  uint32_t* sched_hs = hot && hs == l.s ? nullptr : l.sched_hs;
   // the hot segment on the key-segmented (slice) kernel: one workgroup per CU walks contiguous slices
   // of the length-sorted segment (count = the segment's entries, so no row segment is ever reached).
   // E's hot AES key alone 2.94 -> 2.54 ns per packet, hot + Initial keys 3.03 -> 2.76; the whole
   // config-E batch unchanged (its ChaCha20 list after the multi-key kernel on s is the longer chain;
   // profiles/r06q_*). MQ_AES_HOT_SEG=0: the tile kernel.
-  const bool hot_seg = hot && opt(Opt::AesHotSeg) != 0;
-  const uint32_t seg_blocks = (uint32_t)(cus > 0 ? cus : 256);
-  if (hot_seg) {
-    if (open)
-      hipLaunchKernelGGL(opens_of(ghot), dim3(seg_blocks), dim3(64 * aes_seg_waves()), 0, hs, kt, n_rows, arena,
-                         arena_len, desc, index, hot + 1, hot, (const uint32_t*)nullptr, status, pn_out, hpm, sched_hs);
-    else
-      hipLaunchKernelGGL(seals_of(ghot), dim3(seg_blocks), dim3(64 * aes_seg_waves()), 0, hs, kt, n_rows, arena,
-                         arena_len, desc, index, hot + 1, hot, (const uint32_t*)nullptr, status, sched_hs);
-  }
-  if (open) {
-    if (hot && !hot_seg)
-      hipLaunchKernelGGL(open1_of(ghot), dim3(hot_blocks),
-                         dim3(64 * aes_waves(true)), 0, hs, kt, n_rows, arena, arena_len, desc, n, index, n_dev, hot,
-                         status, pn_out, hpm, sched_hs);
-    hipLaunchKernelGGL(n_rows == 1 ? mq_aes_open1_kernel : mq_aes_open_kernel, dim3(blocks), dim3(64 * waves),
-                       0, s, kt, n_rows, arena, arena_len, desc, n, index, n_dev, hot, status, pn_out, hpm, sched_s);
-  } else {
-    if (hot && !hot_seg)
-      hipLaunchKernelGGL(seal1_of(ghot), dim3(hot_blocks),
-                         dim3(64 * aes_waves(true)), 0, hs, kt, n_rows, arena, arena_len, desc, n, index, n_dev, hot,
-                         status, sched_hs);
-    hipLaunchKernelGGL(n_rows == 1 ? mq_aes_seal1_kernel : mq_aes_seal_kernel, dim3(blocks), dim3(64 * waves),
-                       0, s, kt, n_rows, arena, arena_len, desc, n, index, n_dev, hot, status, sched_s);
-  }
+  if (hot && b.sw.aes_hot_seg != 0)
+    launch(seals_of(ghot), opens_of(ghot), seg_grid, seg_block, hs, sched_hs, l.index, hot + 1, hot,
+           (const uint32_t*)nullptr);
+  else if (hot)
+    launch(seal1_of(ghot), open1_of(ghot), dim3(aes_grid(tiles, aes_waves(true), b.cus)), dim3(64 * aes_waves(true)), hs,
+           sched_hs, n, l.index, l.n_dev, hot);
+  launch(n_rows == 1 ? mq_aes_seal1_kernel : mq_aes_seal_kernel, n_rows == 1 ? mq_aes_open1_kernel : mq_aes_open_kernel,
+         dim3(blocks), dim3(64 * waves), l.s, l.sched, n, l.index, l.n_dev, hot);
   return hipGetLastError();
 }
 
@@ -1185,11 +1155,11 @@ __global__ __launch_bounds__(256) void mq_mixed_hp_kernel(
   hpm[item] = prepass_decode_words(b0, wd[0], d, m0, m1);
 }
 
-hipError_t mq_launch_mixed_open_hp(const KeyRow* kt, uint32_t n_rows, const uint8_t* arena, uint64_t arena_len,
-                                   const mq_pkt_desc* desc, uint32_t n, uint2* hpm, hipStream_t s) {
+hipError_t mq_launch_mixed_open_hp(const mq::BatchArgs& b, uint32_t n, hipStream_t s) {
   const uint32_t blocks = (n + 255) / 256;
   if (blocks == 0) return hipSuccess;
-  hipLaunchKernelGGL(mq_mixed_hp_kernel, dim3(blocks), dim3(256), 0, s, kt, n_rows, arena, arena_len, desc, n, hpm);
+  hipLaunchKernelGGL(mq_mixed_hp_kernel, dim3(blocks), dim3(256), 0, s, b.kt, b.n_rows, b.arena, b.arena_len, b.desc, n,
+                     b.hpm);
   return hipGetLastError();
 }
 

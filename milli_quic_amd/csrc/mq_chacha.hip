@@ -15,7 +15,7 @@
 //         keystream XOR (held first block + the rest); failed packets are never stored.
 #include "mq_tile.h"
 #include "mq_build.h"
-#include "mq_opts.h"
+#include "mq_launch.h"
 
 #include <cstdlib>
 #include <type_traits>
@@ -1591,16 +1591,32 @@ int mq_chacha_flat_kind(uint64_t bpp) {
   return bpp <= kNarrowAvg ? 0 : bpp <= kLongAvg0 ? 1 : bpp <= kLongAvg1 ? 2 : 3;
 }
 
-hipError_t mq_launch_chacha(bool open, const KeyRow* kt, uint32_t n_rows, uint8_t* arena,
-                            uint64_t arena_len, const mq_pkt_desc* desc, uint32_t n,
-                            const uint32_t* index, const uint32_t* n_dev, uint8_t* status,
-                            uint64_t* pn_out, uint2* hpm, bool own_hp, hipStream_t s, int cus, uint32_t* sched,
-                            int64_t single_row, bool persistent, const uint32_t* reg, uint64_t bpp) {
+// The seal / open kernels of each family; one: its single-key kernels
+static auto cc_seal_of(bool one) { return one ? mq_chacha_seal1_kernel : mq_chacha_seal_kernel; }
+static auto cc_open_of(bool one) { return one ? mq_chacha_open1_kernel : mq_chacha_open_kernel; }
+static auto cc_list_seal_of(bool one) { return one ? mq_chacha_seal_list1_kernel : mq_chacha_seal_list_kernel; }
+static auto cc_list_open_of(bool one) { return one ? mq_chacha_open_list1_kernel : mq_chacha_open_list_kernel; }
+static auto cc_lgrid_seal_of(bool one) { return one ? mq_chacha_seal_lgrid1_kernel : mq_chacha_seal_lgrid_kernel; }
+static auto cc_lgrid_open_of(bool one) { return one ? mq_chacha_open_lgrid1_kernel : mq_chacha_open_lgrid_kernel; }
+// flat batches off the 10-KiB octet tiles: img 0 the narrow kernels, 1 / 2 the 13- / 20-KiB images
+static auto cc_flat_seal_of(int img, bool one) {
+  return img == 0   ? (one ? mq_chacha_seal_narrow1_kernel : mq_chacha_seal_narrow_kernel)
+         : img == 2 ? (one ? mq_chacha_seal_longer1_kernel : mq_chacha_seal_longer_kernel)
+                    : (one ? mq_chacha_seal_long1_kernel : mq_chacha_seal_long_kernel);
+}
+static auto cc_flat_open_of(int img, bool one) {
+  return img == 0   ? (one ? mq_chacha_open_narrow1_kernel : mq_chacha_open_narrow_kernel)
+         : img == 2 ? (one ? mq_chacha_open_longer1_kernel : mq_chacha_open_longer_kernel)
+                    : (one ? mq_chacha_open_long1_kernel : mq_chacha_open_long_kernel);
+}
+
+hipError_t mq_launch_chacha(const mq::BatchArgs& b, const mq::TileLaunch& l) {
+  const uint32_t n = l.n, n_rows = b.n_rows;
   const uint32_t tiles = (n + kPktsPerTile - 1) / kPktsPerTile;
   if (tiles == 0) return hipSuccess;
-  if (open && hpm && own_hp) {  // !own_hp: mq_launch_mixed_hp covers both suites' lists
-    hipLaunchKernelGGL(mq_chacha_open_hp_kernel<true>, dim3((n + 255) / 256), dim3(256), 0, s, kt, n_rows, arena,
-                       arena_len, desc, n, index, n_dev, hpm);
+  if (b.open && b.hpm && l.own_hp) {  // !own_hp: mq_launch_mixed_hp covers both suites' lists
+    hipLaunchKernelGGL(mq_chacha_open_hp_kernel<true>, dim3((n + 255) / 256), dim3(256), 0, l.s, b.kt, n_rows, b.arena,
+                       b.arena_len, b.desc, n, l.index, l.n_dev, b.hpm);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
   }
@@ -1609,87 +1625,55 @@ hipError_t mq_launch_chacha(bool open, const KeyRow* kt, uint32_t n_rows, uint8_
   // list then costs 1024 workgroups, not a grid over the list capacity), else on the one-shot grid,
   // which measured 1.1 % faster on config E (r04q: 557.9 vs 551.6 GiB/s, three alternating runs).
   // MQ_CC_LIST=0 / 1 (diagnostic, mq_opts.h: tests run both grids on one batch) forces either.
-  const long forced = mq::opt(mq::Opt::CcList);
-  if (forced >= 0) persistent = forced != 0;
+  const bool persistent = b.sw.cc_list >= 0 ? b.sw.cc_list != 0 : l.persistent;
   // single_row >= 0: every packet of the list is on that row (the single-key kernels)
-  const bool one = index && single_row >= 0 && (uint64_t)single_row < n_rows;
-  const KeyRow* kl = one ? kt + single_row : kt;
+  const bool one = l.index && l.single_row >= 0 && (uint64_t)l.single_row < n_rows;
+  const KeyRow* kl = one ? b.kt + l.single_row : b.kt;
   // MQ_CC_SPAN=0 (diagnostic, mq_opts.h: tests run both copies on one batch): no span tiles in the
   // octet-tile kernels (chacha_tile reads the bit off n_rows)
   // MQ_CC_WGMAC=0 (likewise): the per-wave MAC in the kernels with the workgroup MAC phase
-  const uint32_t nr = n_rows | (mq::opt(mq::Opt::CcSpan) == 0 ? kCcNoSpan : 0u) |
-                      (mq::opt(mq::Opt::CcWgMac) == 0 ? kCcNoWgMac : 0u);
-  if (index && persistent) {
-    const uint32_t per = (uint32_t)(cus > 0 ? cus : 256) * 4u, grid = blocks < per ? blocks : per;
-    if (open)
-      hipLaunchKernelGGL(one ? mq_chacha_open_list1_kernel : mq_chacha_open_list_kernel, dim3(grid),
-                         dim3(kWave * kCcWaves), kLdsBytes * kCcWaves, s, kl, nr, arena, arena_len, desc, n, index,
-                         n_dev, status, pn_out, hpm, sched, reg);
+  const uint32_t nr = n_rows | (b.sw.cc_span == 0 ? kCcNoSpan : 0u) | (b.sw.cc_wgmac == 0 ? kCcNoWgMac : 0u);
+  const dim3 block(kWave * kCcWaves);
+  constexpr uint32_t kLds = kLdsBytes * kCcWaves;
+  // One kernel of a family's pair: both take the key rows, the row word, the arena, the descriptors,
+  // n, the family's own arguments (mid) and the status; the open kernel then pn_out and hpm.
+  auto launch = [&](auto seal, auto open, uint32_t grid, uint32_t lds, const KeyRow* rows, uint32_t row_word,
+                    auto... mid) {
+    if (b.open)
+      hipLaunchKernelGGL(open, dim3(grid), block, lds, l.s, rows, row_word, b.arena, b.arena_len, b.desc, n, mid...,
+                         b.status, b.pn_out, b.hpm);
+    else  // seal: header protection runs inside the tile kernel (the pool's HP blocks, cc_pool_run)
+      hipLaunchKernelGGL(seal, dim3(grid), block, lds, l.s, rows, row_word, b.arena, b.arena_len, b.desc, n, mid...,
+                         b.status);
+    return hipGetLastError();
+  };
+  if (l.index && persistent) {  // its kernels end on the schedule slot and the regions instead
+    const uint32_t per = (uint32_t)(b.cus > 0 ? b.cus : 256) * 4u, grid = blocks < per ? blocks : per;
+    if (b.open)
+      hipLaunchKernelGGL(cc_list_open_of(one), dim3(grid), block, kLds, l.s, kl, nr, b.arena, b.arena_len, b.desc, n,
+                         l.index, l.n_dev, b.status, b.pn_out, b.hpm, l.sched, l.reg);
     else
-      hipLaunchKernelGGL(one ? mq_chacha_seal_list1_kernel : mq_chacha_seal_list_kernel, dim3(grid),
-                         dim3(kWave * kCcWaves), kLdsBytes * kCcWaves, s, kl, nr, arena, arena_len, desc, n, index,
-                         n_dev, status, sched, reg);
+      hipLaunchKernelGGL(cc_list_seal_of(one), dim3(grid), block, kLds, l.s, kl, nr, b.arena, b.arena_len, b.desc, n,
+                         l.index, l.n_dev, b.status, l.sched, l.reg);
     return hipGetLastError();
   }
-  if (index) {  // one-shot grid over the list capacity (every region's tiles fit: a tile holds >= 8 entries)
-    if (open)
-      hipLaunchKernelGGL(one ? mq_chacha_open_lgrid1_kernel : mq_chacha_open_lgrid_kernel, dim3(blocks),
-                         dim3(kWave * kCcWaves), kLdsBytes * kCcWaves, s, kl, nr, arena, arena_len, desc, n, index,
-                         reg, status, pn_out, hpm);
-    else
-      hipLaunchKernelGGL(one ? mq_chacha_seal_lgrid1_kernel : mq_chacha_seal_lgrid_kernel, dim3(blocks),
-                         dim3(kWave * kCcWaves), kLdsBytes * kCcWaves, s, kl, nr, arena, arena_len, desc, n, index,
-                         reg, status);
-    return hipGetLastError();
-  }
+  // one-shot grid over the list capacity (every region's tiles fit: a tile holds >= 8 entries)
+  if (l.index) return launch(cc_lgrid_seal_of(one), cc_lgrid_open_of(one), blocks, kLds, kl, nr, l.index, l.reg);
   // Flat batches: the kernel family from the bytes per packet (mq_chacha_flat_kind). MQ_CC_NARROW=0 / 1
   // and MQ_CC_LONG=0 / 1 / 2 (diagnostic, mq_opts.h: tests run several kernels on one batch) force
   // the wide / narrow kernels and the 10-, 13- or 20-KiB images.
-  if (!index) {
-    const int kind = mq_chacha_flat_kind(bpp);
-    bool narrow = kind == 0;
-    const long fn = mq::opt(mq::Opt::CcNarrow);
-    if (fn >= 0) narrow = fn == 1;
-    if (narrow) {
-      const uint32_t nb = (uint32_t)(((uint64_t)n + kWave * kCcWaves - 1) / (kWave * kCcWaves));
-      if (open)
-        hipLaunchKernelGGL(n_rows == 1 ? mq_chacha_open_narrow1_kernel : mq_chacha_open_narrow_kernel, dim3(nb),
-                           dim3(kWave * kCcWaves), kLdsBytes * kCcWaves, s, kt, n_rows, arena, arena_len, desc, n,
-                           status, pn_out, hpm);
-      else
-        hipLaunchKernelGGL(n_rows == 1 ? mq_chacha_seal_narrow1_kernel : mq_chacha_seal_narrow_kernel, dim3(nb),
-                           dim3(kWave * kCcWaves), kLdsBytes * kCcWaves, s, kt, n_rows, arena, arena_len, desc, n,
-                           status);
-      return hipGetLastError();
-    }
-    int img = kind >= 2 ? kind - 1 : 0;  // 0: 10 KiB, 1: 13 KiB, 2: 20 KiB
-    const long fl = mq::opt(mq::Opt::CcLong);
-    if (fl >= 0) img = fl >= 2 ? 2 : (int)fl;
-    const bool o1 = n_rows == 1;
-    if (img) {
-      const uint32_t lds = (img == 2 ? kLongerImg : kLongImg) * kCcWaves;
-      if (open)
-        hipLaunchKernelGGL(img == 2 ? (o1 ? mq_chacha_open_longer1_kernel : mq_chacha_open_longer_kernel)
-                                    : (o1 ? mq_chacha_open_long1_kernel : mq_chacha_open_long_kernel),
-                           dim3(blocks), dim3(kWave * kCcWaves), lds, s, kt, nr, arena, arena_len, desc, n, status,
-                           pn_out, hpm);
-      else
-        hipLaunchKernelGGL(img == 2 ? (o1 ? mq_chacha_seal_longer1_kernel : mq_chacha_seal_longer_kernel)
-                                    : (o1 ? mq_chacha_seal_long1_kernel : mq_chacha_seal_long_kernel),
-                           dim3(blocks), dim3(kWave * kCcWaves), lds, s, kt, nr, arena, arena_len, desc, n, status);
-      return hipGetLastError();
-    }
+  const int kind = mq_chacha_flat_kind(b.bpp);
+  const bool o1 = n_rows == 1;
+  if (b.sw.cc_narrow >= 0 ? b.sw.cc_narrow == 1 : kind == 0) {
+    const uint32_t nb = (uint32_t)(((uint64_t)n + kWave * kCcWaves - 1) / (kWave * kCcWaves));
+    return launch(cc_flat_seal_of(0, o1), cc_flat_open_of(0, o1), nb, kLds, b.kt, n_rows);
   }
-  if (open)
-    hipLaunchKernelGGL(n_rows == 1 || one ? mq_chacha_open1_kernel : mq_chacha_open_kernel, dim3(blocks),
-                       dim3(kWave * kCcWaves), kLdsBytes * kCcWaves, s, kl, nr, arena, arena_len, desc, n, index,
-                       n_dev, status, pn_out, hpm);
-  if (open) return hipGetLastError();
-  // seal: header protection runs inside the tile kernel (the pool's HP blocks, cc_pool_run)
-  hipLaunchKernelGGL(n_rows == 1 || one ? mq_chacha_seal1_kernel : mq_chacha_seal_kernel, dim3(blocks),
-                     dim3(kWave * kCcWaves), kLdsBytes * kCcWaves, s, kl, nr, arena, arena_len, desc, n, index,
-                     n_dev, status);
-  return hipGetLastError();
+  int img = kind >= 2 ? kind - 1 : 0;  // 0: 10 KiB, 1: 13 KiB, 2: 20 KiB
+  if (b.sw.cc_long >= 0) img = b.sw.cc_long >= 2 ? 2 : (int)b.sw.cc_long;
+  if (img)
+    return launch(cc_flat_seal_of(img, o1), cc_flat_open_of(img, o1), blocks, (img == 2 ? kLongerImg : kLongImg) * kCcWaves,
+                  b.kt, nr);
+  return launch(cc_seal_of(o1), cc_open_of(o1), blocks, kLds, b.kt, nr, l.index, l.n_dev);
 }
 
 hipError_t mq_launch_chacha_protect(const KeyRow* kt, uint32_t n_rows, const mq_conn_send* conns, uint32_t n_conns,

@@ -29,6 +29,7 @@
 #include <stddef.h>
 
 #include "mq_aes.h"
+#include "mq_launch.h"
 
 namespace mq {
 

@@ -17,68 +17,36 @@
 #include <vector>
 
 #include "mq_device.h"
-#include "mq_opts.h"
+#include "mq_launch.h"
 #include "mq_resident.h"
 #include "mq_route.h"
 #include "mq_runtime.h"
 
 using mq::KeyRow;
 
-int mq_chacha_flat_kind(uint64_t bpp);  // mq_chacha.hip
-int mq_aes_flat_lanes(uint64_t bpp);    // mq_aes.hip
-int mq_aes_list_lanes();                // mq_aes.hip
-bool mq_partition_keyed(uint32_t n, uint32_t n_rows);  // mq_partition.hip
-
 // ---- diagnostic switches (mq_opts.h) ---------------------------------------------------------
-namespace {
-const char* const kOptNames[(int)mq::Opt::Count] = {
-    "MQ_CC_NARROW", "MQ_CC_LONG",  "MQ_CC_LIST",           "MQ_HP_FORK", "MQ_AES_SEG",
-    "MQ_PROTECT_FUSED", "MQ_RESIDENT", "MQ_RESIDENT_TIMEOUT_US", "MQ_RECV_SEG", "MQ_AES_HOT_SEG", "MQ_AES_NARROW",
-    "MQ_CC_SPAN", "MQ_CC_WGMAC"};
-std::atomic<long> g_opts[(int)mq::Opt::Count];
-std::once_flag g_opts_once;
-void opts_init() {  // once: the environment's values (shell-driven diagnostics keep working)
-  std::call_once(g_opts_once, [] {
-    for (int k = 0; k < (int)mq::Opt::Count; ++k) {
-      const char* e = std::getenv(kOptNames[k]);
-      long v = -1;
-      if (e && *e) {
-        char* end = nullptr;
-        v = std::strtol(e, &end, 10);
-        if (end == e || v < 0) v = -1;  // not a number: unset
-      }
-      g_opts[k].store(v, std::memory_order_relaxed);
-    }
-  });
-}
-}  // namespace
-
-long mq::opt(mq::Opt o) {
-  opts_init();
-  return g_opts[(int)o].load(std::memory_order_relaxed);
-}
-
 extern "C" int mq_debug_option(const char* name, long value) {
-  if (!name) return MQ_ERR_INVALID_ARG;
-  opts_init();
-  for (int k = 0; k < (int)mq::Opt::Count; ++k)
-    if (std::strcmp(name, kOptNames[k]) == 0) {
-      g_opts[k].store(value < 0 ? -1 : value, std::memory_order_relaxed);
-      return MQ_OK;
-    }
-  return MQ_ERR_INVALID_ARG;
+  return name && mq::opt_set(name, value) ? MQ_OK : MQ_ERR_INVALID_ARG;
+}
+
+extern "C" long mq_debug_option_get(const char* name) {
+  const mq::Opt o = name ? mq::opt_find(name) : mq::Opt::Count;
+  return o == mq::Opt::Count ? -2 : mq::opt(o);
+}
+
+// A batch's bytes per packet (n > 0): MQ_BATCH_LEN_HINT in the hint's high half; without it the
+// arena's bytes per packet stand in for the batch's (right when the arena holds just this batch)
+static uint64_t batch_bpp(uint64_t arena_len, uint32_t n, uint32_t suite_hint) {
+  const uint64_t len_hint = suite_hint >> 16;
+  return len_hint ? len_hint : (arena_len + n - 1) / n;
 }
 
 extern "C" int mq_debug_chacha_flat_kind(uint64_t arena_len, uint32_t n, uint32_t suite_hint) {
-  const uint64_t len_hint = suite_hint >> 16;
-  if (n == 0) return -1;
-  return mq_chacha_flat_kind(len_hint ? len_hint : (arena_len + n - 1) / n);
+  return n == 0 ? -1 : mq_chacha_flat_kind(batch_bpp(arena_len, n, suite_hint));
 }
 
 extern "C" int mq_debug_aes_flat_kind(uint64_t arena_len, uint32_t n, uint32_t suite_hint) {
-  const uint64_t len_hint = suite_hint >> 16;
-  if (n == 0) return -1;
-  return mq_aes_flat_lanes(len_hint ? len_hint : (arena_len + n - 1) / n);
+  return n == 0 ? -1 : mq_aes_flat_lanes(mq::switches().aes_narrow, batch_bpp(arena_len, n, suite_hint));
 }
 
 // The path a batch's AES-128-GCM packets take, decided here and nowhere else: batch() launches what
@@ -87,14 +55,13 @@ extern "C" int mq_debug_aes_flat_kind(uint64_t arena_len, uint32_t n, uint32_t s
 //   2^30 packets): the single-key kernels for one row, else the multi-key kernel;
 //   otherwise the partition, whose list 0 runs either as the hot key's segment on a single-key
 //   kernel beside the multi-key kernel, or whole on the key-segmented single-key kernels: keys with
-//   many packets each (on average >= kSegPackets per row) in the keyed layout. MQ_AES_SEG
+//   many packets each (on average >= kSegPackets per row) in the keyed layout. seg_opt: MQ_AES_SEG
 //   (diagnostic): 0 = never, 1 = whenever the layout is keyed.
 enum AesListKind { kAesFlatSingle = 0, kAesFlatMulti = 1, kAesPartitionHot = 2, kAesKeySegments = 3 };
-static AesListKind aes_list_kind(uint32_t suite_hint, uint32_t n, uint32_t n_rows, bool has_ws) {
+static AesListKind aes_list_kind(long seg_opt, uint32_t suite_hint, uint32_t n, uint32_t n_rows, bool has_ws) {
   if (suite_hint == MQ_SUITE_AES128GCM && (n_rows == 1 || !has_ws || n > (1u << 30)))
     return n_rows == 1 ? kAesFlatSingle : kAesFlatMulti;
   constexpr uint32_t kSegPackets = 512;
-  const long seg_opt = mq::opt(mq::Opt::AesSeg);
   const bool seg = seg_opt != 0 && (seg_opt == 1 || (uint64_t)n >= (uint64_t)kSegPackets * n_rows) &&
                    mq_partition_keyed(n, n_rows);
   return seg ? kAesKeySegments : kAesPartitionHot;
@@ -102,100 +69,13 @@ static AesListKind aes_list_kind(uint32_t suite_hint, uint32_t n, uint32_t n_row
 
 extern "C" int mq_debug_aes_list_kind(uint32_t n, uint32_t n_rows) {
   if (n == 0 || n_rows == 0) return -1;
-  const AesListKind kind = aes_list_kind(MQ_SUITE_AES128GCM, n, n_rows, true);
-  int lanes = mq_aes_list_lanes();                                                   // segments of a partition list
-  if (kind == kAesFlatSingle) lanes = mq::opt(mq::Opt::AesNarrow) >= 0 ? mq_aes_flat_lanes(0) : 0;  // else by bytes per packet
+  const mq::Switches sw = mq::switches();
+  const AesListKind kind = aes_list_kind(sw.aes_seg, MQ_SUITE_AES128GCM, n, n_rows, true);
+  int lanes = mq_aes_list_lanes(sw.aes_narrow);  // segments of a partition list
+  if (kind == kAesFlatSingle) lanes = sw.aes_narrow >= 0 ? mq_aes_flat_lanes(sw.aes_narrow, 0) : 0;  // else by bytes per packet
   if (kind == kAesFlatMulti) lanes = 8;
   return (int)kind | lanes << 8;
 }
-
-extern "C" long mq_debug_option_get(const char* name) {
-  if (!name) return -2;
-  for (int k = 0; k < (int)mq::Opt::Count; ++k)
-    if (std::strcmp(name, kOptNames[k]) == 0) return mq::opt((mq::Opt)k);
-  return -2;
-}
-
-// launchers defined in the .hip translation units
-hipError_t mq_launch_chacha(bool open, const KeyRow* kt, uint32_t n_rows, uint8_t* arena,
-                            uint64_t arena_len, const mq_pkt_desc* desc, uint32_t n,
-                            const uint32_t* index, const uint32_t* n_dev, uint8_t* status,
-                            uint64_t* pn_out, uint2* hpm, bool own_hp, hipStream_t s, int cus, uint32_t* sched,
-                            int64_t single_row, bool persistent, const uint32_t* reg, uint64_t bpp);
-const uint32_t* mq_partition_regions(const uint32_t* counts);
-hipError_t mq_launch_chacha_hp(const KeyRow* kt, uint32_t n_rows, const uint32_t* key_ids,
-                               const uint8_t* samples, uint8_t* masks, uint32_t n, hipStream_t s);
-hipError_t mq_launch_aes(bool open, const KeyRow* kt, uint32_t n_rows, uint8_t* arena,
-                         uint64_t arena_len, const mq_pkt_desc* desc, uint32_t n,
-                         const uint32_t* index, const uint32_t* n_dev, const uint32_t* hot,
-                         uint8_t* status, uint64_t* pn_out, uint2* hpm, bool own_hp, hipStream_t s,
-                         hipStream_t hot_stream, int cus, const uint32_t* rowseg, uint32_t* sched_s,
-                         uint32_t* sched_hs, uint64_t bpp = 0);
-const uint32_t* mq_partition_rowseg(uint32_t n, uint32_t n_rows, const uint32_t* counts);
-hipError_t mq_launch_mixed_open_hp(const KeyRow* kt, uint32_t n_rows, const uint8_t* arena, uint64_t arena_len,
-                                   const mq_pkt_desc* desc, uint32_t n, uint2* hpm, hipStream_t s);
-hipError_t mq_launch_aes_hp(const KeyRow* kt, uint32_t n_rows, const uint32_t* key_ids,
-                            const uint8_t* samples, uint8_t* masks, uint32_t n, hipStream_t s);
-hipError_t mq_launch_partition(const KeyRow* kt, uint32_t n_rows, const mq_pkt_desc* desc, uint32_t n,
-                               uint32_t* list, uint32_t* codes, uint32_t* counts, hipStream_t s, bool skip_unkeyed,
-                               const uint32_t* live);
-size_t mq_partition_workspace(uint32_t n);
-void mq_partition_layout(uint32_t n, size_t* codes_off, size_t* counts_off);
-uint32_t mq_partition_list_cap(uint32_t n);
-hipError_t mq_launch_derive_initial(const mq::MQDeriveConsts& k, const uint8_t* dcids, const uint8_t* dcid_lens,
-                                    uint32_t n, KeyRow* rows, mq_key_material* km_out, uint8_t* status,
-                                    hipStream_t s);
-hipError_t mq_launch_derive_keys(const mq::MQRekeyConsts& k, uint32_t suite, const uint8_t* secrets, uint32_t first_row,
-                                 const uint32_t* row_idx, uint32_t n, KeyRow* rows, uint32_t n_rows,
-                                 mq_key_material* km_out, uint8_t* status, hipStream_t s);
-hipError_t mq_launch_key_update(const mq::MQRekeyConsts& k, uint8_t* secrets, const uint32_t* src_rows,
-                                const uint32_t* dst_rows, uint32_t n, KeyRow* rows, uint32_t n_rows,
-                                mq_key_material* km_out, uint8_t* status, hipStream_t s);
-hipError_t mq_launch_recv_rekey(const mq::MQRekeyConsts& k, mq_conn_recv* conns, uint32_t n_conns, uint8_t* secrets,
-                                const uint32_t* pool_first, KeyRow* rows, uint32_t n_rows, uint8_t* status,
-                                hipStream_t s);
-hipError_t mq_launch_build(const KeyRow* kt, uint32_t n_rows, const mq_conn_send* conns, uint32_t n_conns,
-                           const uint8_t* frames, uint64_t frames_len, uint8_t* out, uint64_t out_len,
-                           const mq_send_req* req, uint32_t n, mq_pkt_desc* desc, uint8_t* bstatus,
-                           uint32_t* pkt_len, uint32_t suite_hint, hipStream_t s);
-hipError_t mq_launch_send_status(const uint8_t* bstatus, uint8_t* status, uint32_t n, hipStream_t s);
-hipError_t mq_launch_chacha_protect(const KeyRow* kt, uint32_t n_rows, const mq_conn_send* conns, uint32_t n_conns,
-                                    const uint8_t* frames, uint64_t frames_len, uint8_t* out, uint64_t out_len,
-                                    const mq_send_req* req, uint32_t n, uint32_t suite_hint, uint8_t* status,
-                                    uint32_t* pkt_len, hipStream_t s);
-size_t mq_recv_workspace(uint32_t n_dgrams, uint32_t max_pkts, uint32_t n_conns, size_t open_ws_bytes);
-void mq_recv_trace(const char* what, uint32_t n_dgrams, uint32_t max_pkts, uint32_t n_conns, void* ws_ptr,
-                   size_t open_ws_bytes, uint32_t seg, hipStream_t s);
-uint32_t mq_recv_seg_len();
-hipError_t mq_recv_front(const KeyRow* kt, uint32_t n_rows, mq_conn_recv* conns, uint32_t n_conns, uint8_t* arena,
-                         uint64_t arena_len, const mq_dgram* dg, uint32_t n_dgrams, uint32_t max_pkts,
-                         uint32_t* n_pkts, mq_recv_pkt* out, void* ws_ptr, size_t open_ws_bytes, mq::MQRecvPass* pass,
-                         uint32_t seg, hipStream_t s);
-hipError_t mq_recv_walk(const KeyRow* kt, uint32_t n_rows, mq_conn_recv* conns, uint32_t n_conns,
-                        uint32_t n_dgrams, uint32_t max_pkts, mq_recv_pkt* out, void* ws_ptr, size_t open_ws_bytes,
-                        bool final_walk, bool verify, uint32_t walk_idx, uint32_t seg, hipStream_t s);
-hipError_t mq_recv_retry(uint32_t n_dgrams, uint32_t max_pkts, uint32_t n_conns, void* ws_ptr, size_t open_ws_bytes,
-                         hipStream_t s);
-hipError_t mq_recv_outcomes(uint32_t n_dgrams, uint32_t max_pkts, uint32_t n_conns, void* ws_ptr,
-                            size_t open_ws_bytes, hipStream_t s);
-hipError_t mq_launch_record_inner(const uint8_t* arena, uint64_t arena_len, const mq_pkt_desc* desc, uint32_t n,
-                                  uint8_t* status, uint64_t* info, hipStream_t s);
-size_t mq_route_workspace(uint32_t n);  // mq_route.hip
-hipError_t mq_launch_route(const mq::CidTableDev& t, const uint8_t* arena, uint64_t arena_len, mq_dgram* dg, uint32_t n,
-                           uint32_t sdl, const mq_route_admit* admit, uint8_t* status, void* workspace,
-                           hipStream_t s);
-hipError_t mq_launch_cid_insert(const mq::CidTableDev& t, const uint8_t* cids, const uint8_t* lens,
-                                const uint32_t* conn, uint32_t n, uint8_t* status, hipStream_t s);
-hipError_t mq_launch_cid_remove(const mq::CidTableDev& t, const uint8_t* cids, const uint8_t* lens, uint32_t n,
-                                uint8_t* status, hipStream_t s);
-hipError_t mq_launch_cid_compact(const mq::CidTableDev& t, void* to, hipStream_t s);
-int mq_resident_call(int dev, const mq::ResReq& q, uint64_t uid, const uint8_t* aad, const uint8_t* body, uint8_t* out,
-                     size_t out_off, size_t out_len, int* status, uint32_t* mask);
-#ifdef MQ_STAMPS
-void mq_stamps_set_chacha(uint64_t* p);
-void mq_stamps_set_aes(uint64_t* p);
-void mq_stamps_set_part(uint64_t* p);
-#endif
 
 namespace {
 
@@ -591,12 +471,19 @@ int run_one(Scratch& sc, const KeyRow& row, const uint8_t* aad, uint32_t aad_len
   uint64_t* pn = (uint64_t*)(sc.dev + Scratch::kPn);
   // the arena is the whole scratch buffer; the packet sits at offset kHdr. NO_HP: no header
   // protection pass to launch (own_hp false)
-  hipError_t e = row.suite == MQ_SUITE_CHACHA20
-                     ? mq_launch_chacha(open, kt, 1, sc.dev, bytes, dd, 1, nullptr, nullptr, st, pn, nullptr, false, sc.stream,
-                                        0, nullptr, -1, false, nullptr, bytes)
-                     : mq_launch_aes(open, kt, 1, sc.dev, bytes, dd, 1, nullptr, nullptr, nullptr, st, pn, nullptr, false,
-                                     sc.stream, sc.stream, devices().cus(sc.device), nullptr, nullptr, nullptr);
-  if (e != hipSuccess) return MQ_ERR_HIP;
+  const bool chacha = row.suite == MQ_SUITE_CHACHA20;
+  mq::BatchArgs b{};
+  b.open = open;
+  b.kt = kt; b.n_rows = 1;
+  b.arena = sc.dev; b.arena_len = bytes;
+  b.desc = dd;
+  b.status = st; b.pn_out = pn;
+  b.cus = devices().cus(sc.device);
+  b.bpp = chacha ? bytes : 0;  // AES-128-GCM: unknown, so the octet kernels
+  b.sw = mq::switches();
+  mq::TileLaunch l;
+  l.n = 1; l.s = l.hs = sc.stream;
+  if ((chacha ? mq_launch_chacha(b, l) : mq_launch_aes(b, l)) != hipSuccess) return MQ_ERR_HIP;
   // status and the transformed packet in one read-back (the status sits before the packet)
   if ((rc = sc.finish(Scratch::kStatus, Scratch::kHdr - Scratch::kStatus + pkt_len)) != MQ_OK) return rc;
   const int status = sc.host[Scratch::kStatus];
@@ -1032,7 +919,7 @@ size_t mq_batch_workspace_size(uint32_t n) { return ws_align(8 * (size_t)n) + mq
 // passes): device word with the pass's number of keyed descriptors, 0 = the partition publishes
 // empty lists at once (mq_partition.hip). hpm_ready: the open pre-pass values are already in the
 // workspace (the receive walk writes them), so no header-protection pre-pass runs.
-static int batch(bool open, const mq_keytable* kt, uint8_t* arena, uint64_t arena_len,
+static int batch(const mq::Switches& sw, bool open, const mq_keytable* kt, uint8_t* arena, uint64_t arena_len,
                  const mq_pkt_desc* desc, uint32_t n, uint8_t* status, uint64_t* pn_out,
                  uint32_t suite_hint, void* workspace, void* stream, bool recv_pass = false,
                  const uint32_t* live = nullptr, bool hpm_ready = false) {
@@ -1041,23 +928,30 @@ static int batch(bool open, const mq_keytable* kt, uint8_t* arena, uint64_t aren
   DeviceGuard g(kt->device);  // the table's device; `stream` must belong to it
   if (!g.ok()) return MQ_ERR_NO_DEVICE;
   if (n == 0) return MQ_OK;
-  // MQ_BATCH_LEN_HINT in the high half; without it the arena's bytes per packet stand in for the
-  // batch's (right when the arena holds just this batch)
-  const uint64_t len_hint = suite_hint >> 16;
+  const uint64_t bpp = batch_bpp(arena_len, n, suite_hint);
   suite_hint &= 0xFFFFu;
-  const uint64_t bpp = len_hint ? len_hint : (arena_len + n - 1) / n;
-  const int cus = devices().cus(kt->device);
   hipStream_t s = (hipStream_t)stream;
   hipError_t e = hipSuccess;
   uint8_t* ws = (uint8_t*)workspace;
+  mq::BatchArgs b;
+  b.open = open;
+  b.kt = kt->dev; b.n_rows = kt->rows;
+  b.arena = arena; b.arena_len = arena_len;
+  b.desc = desc;
+  b.status = status; b.pn_out = pn_out;
   // open with a workspace: header-protection masks come from the one-lane-per-packet pre-pass
-  uint2* hpm = (open && ws) ? (uint2*)ws : nullptr;
+  b.hpm = (open && ws) ? (uint2*)ws : nullptr;
+  b.cus = devices().cus(kt->device);
+  b.bpp = bpp;
+  b.sw = sw;
+  const AesListKind aes_kind = aes_list_kind(sw.aes_seg, suite_hint, n, kt->rows, ws != nullptr);
+  mq::TileLaunch flat;  // a flat launch: the n descriptors in order on s, with its own pre-pass
+  flat.n = n; flat.s = flat.hs = s; flat.own_hp = true;
   if (suite_hint == MQ_SUITE_CHACHA20) {
-    e = mq_launch_chacha(open, kt->dev, kt->rows, arena, arena_len, desc, n, nullptr, nullptr, status, pn_out, hpm, true,
-                         s, cus, nullptr, -1, false, nullptr, bpp);
-  } else if (suite_hint == MQ_SUITE_AES128GCM && aes_list_kind(suite_hint, n, kt->rows, ws != nullptr) <= kAesFlatMulti) {
-    e = mq_launch_aes(open, kt->dev, kt->rows, arena, arena_len, desc, n, nullptr, nullptr, nullptr, status, pn_out,
-                      hpm, true, s, s, cus, nullptr, sched_slot(kt->device, s), nullptr, bpp);
+    e = mq_launch_chacha(b, flat);
+  } else if (suite_hint == MQ_SUITE_AES128GCM && aes_kind <= kAesFlatMulti) {
+    flat.sched = sched_slot(kt->device, s);
+    e = mq_launch_aes(b, flat);
   } else if (suite_hint == MQ_SUITE_MIXED || suite_hint == MQ_SUITE_AES128GCM) {
     // the two index lists (2 x mq_partition_list_cap(n) entries, holes included) are addressed
     // with 32-bit positions: up to 2^30 packets per mixed batch. An AES batch over several key
@@ -1080,12 +974,12 @@ static int batch(bool open, const mq_keytable* kt, uint8_t* arena, uint64_t aren
     // its blocks to delay — r03f measured that scan 27 -> 85 us and no gain); MQ_HP_FORK=0
     // (diagnostic, mq_opts.h) runs it on s after the partition, as r04 did.
     {
-      const bool hp = open && hpm && !hpm_ready;
-      auto hfork = hp && fork_enabled() && mq::opt(mq::Opt::HpFork) != 0 ? side_streams().fork(kt->device, s, 1)
-                                                                          : mq::SideStreams<HipBackend>::Fork();
-      if (hp && hfork) e = mq_launch_mixed_open_hp(kt->dev, kt->rows, arena, arena_len, desc, n, hpm, hfork.side(0));
-      if (e == hipSuccess) e = mq_launch_partition(kt->dev, kt->rows, desc, n, list, codes, counts, s, recv_pass, live);
-      if (e == hipSuccess && hp && !hfork) e = mq_launch_mixed_open_hp(kt->dev, kt->rows, arena, arena_len, desc, n, hpm, s);
+      const bool hp = open && b.hpm && !hpm_ready;
+      auto hfork = hp && fork_enabled() && sw.hp_fork != 0 ? side_streams().fork(kt->device, s, 1)
+                                                           : mq::SideStreams<HipBackend>::Fork();
+      if (hp && hfork) e = mq_launch_mixed_open_hp(b, n, hfork.side(0));
+      if (e == hipSuccess) e = mq_launch_partition(b, n, list, codes, counts, s, recv_pass, live);
+      if (e == hipSuccess && hp && !hfork) e = mq_launch_mixed_open_hp(b, n, s);
       if (!hfork.join() && e == hipSuccess) e = hipErrorUnknown;
     }  // the fork's entry lock is released before the AES fork below takes it
     if (e != hipSuccess) return MQ_ERR_HIP;
@@ -1098,23 +992,28 @@ static int batch(bool open, const mq_keytable* kt, uint8_t* arena, uint64_t aren
     // stream): mq_runtime.h.
     // Keys with many packets each (aes_list_kind): the key-segmented single-key kernels run list 0
     // whole, no fork (mq_aes.hip aes_seg_tiles)
-    const uint32_t* rowseg = aes_list_kind(suite_hint, n, kt->rows, true) == kAesKeySegments
-                                 ? mq_partition_rowseg(n, kt->rows, counts)
-                                 : nullptr;
+    const uint32_t* rowseg = aes_kind == kAesKeySegments ? mq_partition_rowseg(n, kt->rows, counts) : nullptr;
     auto fork = fork_enabled() && !rowseg ? side_streams().fork(kt->device, s, 1) : mq::SideStreams<HipBackend>::Fork();
     // list 1 stays on s: after the hot segment on its side stream instead it cost E 2 % (the slice
     // kernel) to 10 % (the tile kernel) (profiles/r06r_ab_e_list1_after_hot_rejected.txt)
-    hipStream_t s_hot = fork ? fork.side(0) : s, s_list1 = s;
-    uint32_t* sched_s = sched_slot(kt->device, s);
-    e = mq_launch_aes(open, kt->dev, kt->rows, arena, arena_len, desc, cap, list, counts, counts + 2, status, pn_out,
-                      hpm, false, s, s_hot, cus, rowseg, sched_s, s_hot != s ? sched_slot(kt->device, s_hot) : nullptr);
-    if (e == hipSuccess && aes_only)
-      e = mq_launch_aes(open, kt->dev, kt->rows, arena, arena_len, desc, cap, list + cap, counts + 1, nullptr, status,
-                        pn_out, hpm, false, s_list1, s_list1, cus, nullptr, sched_slot(kt->device, s_list1), nullptr);
-    else if (e == hipSuccess)
-      e = mq_launch_chacha(open, kt->dev, kt->rows, arena, arena_len, desc, cap, list + cap, counts + 1, status,
-                           pn_out, hpm, false, s_list1, cus, sched_slot(kt->device, s_list1), kt->single_row(),
-                           recv_pass, mq_partition_regions(counts), bpp);
+    mq::TileLaunch l0;  // list 0: the hot key's segment beside the other keys' tiles, or the row segments
+    l0.n = cap; l0.index = list; l0.n_dev = counts;
+    l0.s = s; l0.sched = sched_slot(kt->device, s);
+    l0.hot = counts + 2; l0.rowseg = rowseg;
+    l0.hs = fork ? fork.side(0) : s;
+    l0.sched_hs = l0.hs != s ? sched_slot(kt->device, l0.hs) : nullptr;
+    e = mq_launch_aes(b, l0);
+    mq::TileLaunch l1;  // list 1 on s: the ChaCha20 packets, or what an AES batch's AES kernel rejects
+    l1.n = cap; l1.index = list + cap; l1.n_dev = counts + 1;
+    l1.s = l1.hs = s; l1.sched = l0.sched;
+    if (e == hipSuccess && aes_only) {
+      e = mq_launch_aes(b, l1);
+    } else if (e == hipSuccess) {
+      l1.single_row = kt->single_row();
+      l1.persistent = recv_pass;
+      l1.reg = mq_partition_regions(counts);
+      e = mq_launch_chacha(b, l1);
+    }
     // join even after a failed launch, so no side stream runs ahead of s
     if (!fork.join() && e == hipSuccess) e = hipErrorUnknown;
   } else {
@@ -1125,13 +1024,13 @@ static int batch(bool open, const mq_keytable* kt, uint8_t* arena, uint64_t aren
 
 int mq_batch_seal(const mq_keytable* kt, uint8_t* arena, uint64_t arena_len, const mq_pkt_desc* desc,
                   uint32_t n, uint8_t* status, uint32_t suite_hint, void* workspace, void* stream) {
-  return batch(false, kt, arena, arena_len, desc, n, status, nullptr, suite_hint, workspace, stream);
+  return batch(mq::switches(), false, kt, arena, arena_len, desc, n, status, nullptr, suite_hint, workspace, stream);
 }
 
 int mq_batch_open(const mq_keytable* kt, uint8_t* arena, uint64_t arena_len, const mq_pkt_desc* desc,
                   uint32_t n, uint8_t* status, uint64_t* pn_out, uint32_t suite_hint, void* workspace,
                   void* stream) {
-  return batch(true, kt, arena, arena_len, desc, n, status, pn_out, suite_hint, workspace, stream);
+  return batch(mq::switches(), true, kt, arena, arena_len, desc, n, status, pn_out, suite_hint, workspace, stream);
 }
 
 }  // extern "C"
@@ -1275,10 +1174,11 @@ int mq_batch_protect(const mq_keytable* kt, const mq_conn_send* conns, uint32_t 
   if (!g.ok()) return MQ_ERR_NO_DEVICE;
   if (n == 0) return MQ_OK;
   hipStream_t s = (hipStream_t)stream;
+  const mq::Switches sw = mq::switches();  // one setting for the build, every chunk's seal and the status pass
   // ChaCha20 batches (r04): one fused kernel builds each tile's packets into LDS and seals them
   // there (mq_chacha.hip); MQ_PROTECT_FUSED=0 (diagnostic, mq_opts.h: tests compare both) keeps
   // the two-kernel composite below
-  if (mq::opt(mq::Opt::ProtectFused) != 0 && suite_hint == MQ_SUITE_CHACHA20)
+  if (sw.protect_fused != 0 && suite_hint == MQ_SUITE_CHACHA20)
     return mq_launch_chacha_protect(kt->dev, kt->rows, conns, n_conns, frames, frames_len, out, out_len, req, n,
                                     suite_hint, status, pkt_len, s) == hipSuccess
                ? MQ_OK
@@ -1299,7 +1199,7 @@ int mq_batch_protect(const mq_keytable* kt, const mq_conn_send* conns, uint32_t 
     if (mq_launch_build(kt->dev, kt->rows, conns, n_conns, frames, frames_len, out, out_len, req, n, desc, bstatus,
                         pkt_len, suite_hint, s) != hipSuccess)
       return MQ_ERR_HIP;
-    const int sr = batch(false, kt, out, out_len, desc, n, status, nullptr, suite_hint, seal_ws, stream);
+    const int sr = batch(sw, false, kt, out, out_len, desc, n, status, nullptr, suite_hint, seal_ws, stream);
     if (sr != MQ_OK) return sr;
     return mq_launch_send_status(bstatus, status, n, s) == hipSuccess ? MQ_OK : MQ_ERR_HIP;
   }
@@ -1314,7 +1214,7 @@ int mq_batch_protect(const mq_keytable* kt, const mq_conn_send* conns, uint32_t 
       break;
     }
     // the seal workspace is used by one chunk after the other (all on hs)
-    rc = batch(false, kt, out, out_len, desc + lo, hi - lo, status + lo, nullptr, suite_hint, seal_ws, hs);
+    rc = batch(sw, false, kt, out, out_len, desc + lo, hi - lo, status + lo, nullptr, suite_hint, seal_ws, hs);
   }
   if (!fork.join() && rc == MQ_OK) rc = MQ_ERR_HIP;  // s waits for the seals, even after a failure
   if (rc != MQ_OK) return rc;
@@ -1338,7 +1238,8 @@ int mq_batch_recv(const mq_keytable* kt, mq_conn_recv* conns, uint32_t n_conns, 
   hipStream_t s = (hipStream_t)stream;
   const size_t open_ws = mq_batch_workspace_size(max_pkts);
   mq::MQRecvPass p;
-  const uint32_t seg = mq_recv_seg_len();  // once per batch: every walk uses the same segment layout
+  const mq::Switches sw = mq::switches();  // one setting for the walks and all five AEAD passes
+  const uint32_t seg = mq_recv_seg_len(sw.recv_seg);  // every walk uses the same segment layout
   if (mq_recv_front(kt->dev, kt->rows, conns, n_conns, arena, arena_len, dgrams, n_dgrams, max_pkts, n_pkts, pkts,
                     workspace, open_ws, &p, seg, s) != hipSuccess)
     return MQ_ERR_HIP;
@@ -1351,11 +1252,11 @@ int mq_batch_recv(const mq_keytable* kt, mq_conn_recv* conns, uint32_t n_conns, 
   // the first pass) cost a few empty launches; the walks write the open pre-pass values.
   constexpr int kRounds = 2;
   for (int round = 0; round < kRounds; ++round) {
-    int r = batch(true, kt, arena, arena_len, p.d1, max_pkts, p.st1, nullptr, MQ_SUITE_MIXED, p.open_ws, stream, true,
+    int r = batch(sw, true, kt, arena, arena_len, p.d1, max_pkts, p.st1, nullptr, MQ_SUITE_MIXED, p.open_ws, stream, true,
                   p.live1, true);
     if (r != MQ_OK) return r;
     if (mq_recv_retry(n_dgrams, max_pkts, n_conns, workspace, open_ws, s) != hipSuccess) return MQ_ERR_HIP;
-    r = batch(true, kt, arena, arena_len, p.d2, max_pkts, p.st2, nullptr, MQ_SUITE_MIXED, p.open_ws, stream, true,
+    r = batch(sw, true, kt, arena, arena_len, p.d2, max_pkts, p.st2, nullptr, MQ_SUITE_MIXED, p.open_ws, stream, true,
               p.live2, true);
     if (r != MQ_OK) return r;
     if (mq_recv_outcomes(n_dgrams, max_pkts, n_conns, workspace, open_ws, s) != hipSuccess) return MQ_ERR_HIP;
@@ -1369,7 +1270,7 @@ int mq_batch_recv(const mq_keytable* kt, mq_conn_recv* conns, uint32_t n_conns, 
   // reference's (MQ_ERR_CRYPTO) holds plaintext; the final walk left its opening key row and PN in
   // d1 (every other entry has no key row and is skipped), and sealing it again under them restores
   // its bytes as received. Statuses land in the st1 scratch.
-  return batch(false, kt, arena, arena_len, p.d1, max_pkts, p.st1, nullptr, MQ_SUITE_MIXED, p.open_ws, stream, true,
+  return batch(sw, false, kt, arena, arena_len, p.d1, max_pkts, p.st1, nullptr, MQ_SUITE_MIXED, p.open_ws, stream, true,
                p.live1);
 }
 
@@ -1520,13 +1421,13 @@ int mq_record_open(const mq_aead_ctx* ctx, const uint8_t* nonce, size_t nonce_le
 
 int mq_batch_seal_records(const mq_keytable* kt, uint8_t* arena, uint64_t arena_len, const mq_pkt_desc* desc,
                           uint32_t n, uint8_t* status, uint32_t suite_hint, void* workspace, void* stream) {
-  return batch(false, kt, arena, arena_len, desc, n, status, nullptr, suite_hint, workspace, stream);
+  return batch(mq::switches(), false, kt, arena, arena_len, desc, n, status, nullptr, suite_hint, workspace, stream);
 }
 
 int mq_batch_open_records(const mq_keytable* kt, uint8_t* arena, uint64_t arena_len, const mq_pkt_desc* desc,
                           uint32_t n, uint8_t* status, uint64_t* info, uint32_t suite_hint, void* workspace,
                           void* stream) {
-  int rc = batch(true, kt, arena, arena_len, desc, n, status, info, suite_hint, workspace, stream);
+  int rc = batch(mq::switches(), true, kt, arena, arena_len, desc, n, status, info, suite_hint, workspace, stream);
   if (rc != MQ_OK || n == 0) return rc;
   return mq_launch_record_inner(arena, arena_len, desc, n, status, info, (hipStream_t)stream) == hipSuccess
              ? MQ_OK
@@ -1553,6 +1454,7 @@ int mq_batch_time_seal_open(const mq_keytable* kt, uint8_t* arena, uint64_t aren
   if (!g.ok()) return MQ_ERR_NO_DEVICE;
   int rc = MQ_OK;
   hipStream_t s = (hipStream_t)stream;
+  const mq::Switches sw = mq::switches();  // every iteration times the same kernels
   std::vector<hipEvent_t> ev(2 * iters + 1, nullptr);
   auto destroy = [&] {
     for (auto& x : ev)
@@ -1569,9 +1471,9 @@ int mq_batch_time_seal_open(const mq_keytable* kt, uint8_t* arena, uint64_t aren
     return MQ_ERR_HIP;
   }
   for (int i = 0; i < iters; ++i) {
-    rc = mq_batch_seal(kt, arena, arena_len, desc, n, status, suite_hint, workspace, stream);
+    rc = batch(sw, false, kt, arena, arena_len, desc, n, status, nullptr, suite_hint, workspace, stream);
     if (rc == MQ_OK && hipEventRecord(ev[2 * i + 1], s) != hipSuccess) rc = MQ_ERR_HIP;
-    if (rc == MQ_OK) rc = mq_batch_open(kt, arena, arena_len, desc, n, status, pn_out, suite_hint, workspace, stream);
+    if (rc == MQ_OK) rc = batch(sw, true, kt, arena, arena_len, desc, n, status, pn_out, suite_hint, workspace, stream);
     if (rc == MQ_OK && hipEventRecord(ev[2 * i + 2], s) != hipSuccess) rc = MQ_ERR_HIP;
     if (rc != MQ_OK) {  // nothing meaningful to time: drain what was enqueued and stop
       (void)hipStreamSynchronize(s);

@@ -29,7 +29,7 @@
 // scatter from the count kernel's per-packet codes. (r02 start: eight operations with a full vote
 // pass, ~126 us per mixed 2^20-packet partition.)
 #include "mq_tile.h"
-#include "mq_opts.h"
+#include "mq_launch.h"
 
 #include <cstdlib>
 
@@ -652,13 +652,13 @@ const uint32_t* mq_partition_rowseg(uint32_t n, uint32_t n_rows, const uint32_t*
   return keyed_ws((uint32_t*)((uint8_t*)counts + part_align(sizeof(uint32_t) * kMetaWords)), n_rows).rowseg;
 }
 
-hipError_t mq_launch_partition(const KeyRow* kt, uint32_t n_rows, const mq_pkt_desc* desc, uint32_t n,
-                               uint32_t* list, uint32_t* codes, uint32_t* counts, hipStream_t s, bool skip_unkeyed,
-                               const uint32_t* live) {
+hipError_t mq_launch_partition(const mq::BatchArgs& b, uint32_t n, uint32_t* list, uint32_t* codes, uint32_t* counts,
+                               hipStream_t s, bool skip_unkeyed, const uint32_t* live) {
+  const uint32_t n_rows = b.n_rows;
   const uint32_t nblocks = (n + kPartBlock - 1) / kPartBlock;
   // narrow ChaCha20 regions: not for the receive passes (skip_unkeyed); MQ_CC_NARROW=0 (diagnostic /
   // A-B, mq_opts.h) turns them off as it turns off the flat narrow kernels
-  const bool narrow = !skip_unkeyed && mq::opt(mq::Opt::CcNarrow) != 0;
+  const bool narrow = !skip_unkeyed && b.sw.cc_narrow != 0;
   if (nblocks == 0) {  // no lists, no regions
     const hipError_t e = hipMemsetAsync(counts, 0, 4 * sizeof(uint32_t), s);
     return e != hipSuccess ? e : hipMemsetAsync(counts + kMetaReg, 0, 8 * sizeof(uint32_t), s);
@@ -677,9 +677,9 @@ hipError_t mq_launch_partition(const KeyRow* kt, uint32_t n_rows, const mq_pkt_d
   const uint32_t nv = min(kVoteSlices, init_blocks);
   const uint32_t S = min(n, kVoteSample), used = (S + kVoteSlice - 1) / kVoteSlice;  // slices with samples
   const uint32_t grid = max(init_blocks, used);
-  hipLaunchKernelGGL(mq_part_init_kernel, dim3(grid), dim3(kPartThreads), 0, s, kt, n_rows, desc, n, votes,
+  hipLaunchKernelGGL(mq_part_init_kernel, dim3(grid), dim3(kPartThreads), 0, s, b.kt, n_rows, b.desc, n, votes,
                      max(nv, used), (uint4*)list, list_q, (uint4*)bins, bins_q, live, cmax);
-  hipLaunchKernelGGL(mq_part_count_kernel, dim3(nblocks), dim3(kPartThreads), 0, s, kt, n_rows, desc, n, votes,
+  hipLaunchKernelGGL(mq_part_count_kernel, dim3(nblocks), dim3(kPartThreads), 0, s, b.kt, n_rows, b.desc, n, votes,
                      max(nv, used), hot, bins, (uint32_t)skip_unkeyed, live, cmax, counts + kMetaCtot,
                      counts + kMetaDone, cap, counts, seg, cls, reg, (uint32_t)narrow, (uint2*)codes);
   if (bins && n_rows) {

@@ -6,6 +6,7 @@
 // find_inner_content_type (src/tcp_tls/connection.rs:546-556): strip the zero padding, take the
 // last non-zero byte as the content type. One lane per record; the scan is normally one byte.
 #include "mq_device.h"
+#include "mq_launch.h"
 
 using namespace mq;
 

@@ -27,7 +27,7 @@
 #include <cstdlib>
 
 #include "mq_device.h"
-#include "mq_opts.h"
+#include "mq_launch.h"
 
 using namespace mq;
 
@@ -448,10 +448,10 @@ __device__ __forceinline__ uint64_t excl_max_u64(uint64_t v, uint32_t lane, uint
 constexpr uint32_t kSeg = 1024;
 constexpr uint32_t kNoSeg = 0xFFFFFFFFu;  // one segment per run
 // the segment length in packets: kSeg, or MQ_RECV_SEG (diagnostic, mq_opts.h; 0 = one segment per
-// run, the r04 walk). Read ONCE per batch (mq_batch_recv) and handed to every walk: segprev[] slots
-// are indexed by the segment layout, which must not change between the walks of a batch.
-uint32_t mq_recv_seg_len() {
-  const long v = mq::opt(mq::Opt::RecvSeg);
+// run, the r04 walk), v here. Worked out ONCE per batch (mq_batch_recv, from its switch snapshot) and
+// handed to every walk: segprev[] slots are indexed by the segment layout, which must not change
+// between the walks of a batch.
+uint32_t mq_recv_seg_len(long v) {
   if (v < 0) return kSeg;
   return v == 0 ? kNoSeg : (uint32_t)(v < 64 ? 64 : (unsigned long)v & ~63ul);  // whole walk chunks
 }
@@ -993,15 +993,6 @@ RecvWs layout(uint8_t* p, uint32_t n_dgrams, uint32_t max_pkts, uint32_t n_conns
 size_t mq_recv_workspace(uint32_t n_dgrams, uint32_t max_pkts, uint32_t n_conns, size_t open_ws_bytes) {
   return layout(nullptr, n_dgrams, max_pkts, n_conns, open_ws_bytes).bytes;
 }
-
-hipError_t mq_launch_chacha_prepass(const KeyRow* kt, uint32_t n_rows, const uint8_t* arena, uint64_t arena_len,
-                                    const mq_pkt_desc* desc, uint32_t n, uint2* hpm, hipStream_t s);
-hipError_t mq_launch_aes_prepass(const KeyRow* kt, uint32_t n_rows, const uint8_t* arena, uint64_t arena_len,
-                                 const mq_pkt_desc* desc, uint32_t n, uint2* hpm, hipStream_t s);
-
-hipError_t mq_recv_walk(const KeyRow* kt, uint32_t n_rows, mq_conn_recv* conns, uint32_t n_conns,
-                        uint32_t n_dgrams, uint32_t max_pkts, mq_recv_pkt* out, void* ws_ptr, size_t open_ws_bytes,
-                        bool final_walk, bool verify, uint32_t walk_idx, uint32_t seg, hipStream_t s);
 
 // split, header-protection masks, sort, first walk (mq_host.cpp then runs the AEAD passes)
 hipError_t mq_recv_front(const KeyRow* kt, uint32_t n_rows, mq_conn_recv* conns, uint32_t n_conns, uint8_t* arena,

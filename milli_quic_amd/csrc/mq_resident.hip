@@ -26,7 +26,7 @@
 // Dekker-style handshake on `state` / slot 0, so a request posted meanwhile is either served or
 // finds the kernel gone (the host then relaunches it).
 #include "mq_aes.h"
-#include "mq_opts.h"
+#include "mq_launch.h"
 #include "mq_resident.h"
 
 #include <atomic>

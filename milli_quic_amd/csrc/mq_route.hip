@@ -34,6 +34,7 @@
 #include <hipcub/hipcub.hpp>
 
 #include "mq_device.h"
+#include "mq_launch.h"
 #include "mq_route.h"
 
 namespace mq {

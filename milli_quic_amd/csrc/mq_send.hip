@@ -11,6 +11,7 @@
 // packet; the ChaCha20-Poly1305 / AES-128-GCM tile kernels then seal and header-protect those
 // descriptors, and mq_send_status_kernel folds the build statuses in.
 #include "mq_build.h"
+#include "mq_launch.h"
 
 using namespace mq;
 
