@@ -557,6 +557,110 @@ int mq_batch_route(mq_cid_table* t, const uint8_t* arena, uint64_t arena_len, mq
                    uint32_t n_dgrams, uint32_t short_dcid_len, const mq_route_admit* admit,
                    uint8_t* status, void* workspace, void* stream);
 
+/* ---- frame index: the frames of every opened packet as records (mq_batch_frames) -------------------
+ * The step behind mq_batch_recv: dispatch_frames (src/connection/recv.rs:518-545) calling
+ * frame::decode (src/frame/mod.rs:228-461) in a loop, up to the point where the reference hands each
+ * frame to dispatch_frame. Every packet record with status MQ_OK is walked as the reference walks it
+ * (`while pos < payload.len() { decode(&payload[pos..]) }`) and yields one mq_frame per frame other
+ * than PADDING, in packet order and inside a packet in payload order, plus one mq_pkt_frames. The
+ * arena is only read; frame data (CRYPTO, STREAM, NEW_TOKEN, reason bytes) is located, never loaded.
+ *
+ * decode, restated (positions relative to the payload start, which is arena[offset + payload_offset];
+ * the payload ends 16 bytes before offset + len):
+ *  - The type is a varint (read_varint, mod.rs:183-190), so its 2-, 4- and 8-byte encodings are
+ *    accepted; a value above 0x1e is FrameEncodingError. Every field is a varint of any width; a
+ *    varint that starts at or runs past the payload's end is FrameEncodingError.
+ *  - A length field larger than the bytes left is FrameEncodingError (read_bytes, mod.rs:200-207;
+ *    compared in 64 bits). A STREAM frame without the LEN bit takes the rest of the payload.
+ *    NEW_CONNECTION_ID: a CID length over 20 fails before its bytes are counted. An ACK walks
+ *    ack_range_count (gap, range) pairs and fails where the bytes run out.
+ *  - Nothing else is checked (no level-against-type rule, no minimal-encoding rule); an empty payload
+ *    is zero frames and MQ_OK.
+ * On an error the packet's status is MQ_ERR_FRAME, err_pos the position at which the failing decode
+ * started, the records of the frames before it stand (the reference has dispatched them by then) and
+ * flags holds what they accumulated.
+ *
+ * Record fields by type (unused fields are 0; `data` is data_pos / data_len):
+ *   0x01 PING, 0x1e HANDSHAKE_DONE  —
+ *   0x02/0x03 ACK                   v = largest_ack, ack_delay, ack_range_count, first_ack_range; data =
+ *                                   the raw range bytes (ack_ranges, mod.rs:247-254); 0x03: aux =
+ *                                   position of the three ECN counts
+ *   0x04 RESET_STREAM               v = stream_id, error_code, final_size
+ *   0x05 STOP_SENDING               v = stream_id, error_code
+ *   0x06 CRYPTO                     v[1] = offset; data
+ *   0x07 NEW_TOKEN                  data = the token
+ *   0x08-0x0f STREAM                v = stream_id, offset (0 without OFF); data; FIN is type bit 0
+ *   0x10 0x14 0x19 0x12/13 0x16/17  v[0] = the value
+ *   0x11, 0x15                      v = stream_id, limit
+ *   0x18 NEW_CONNECTION_ID          v = sequence_number, retire_prior_to; data = the CID; aux = position
+ *                                   of the 16-byte stateless reset token
+ *   0x1a/0x1b PATH_*                data = the 8 bytes
+ *   0x1c/0x1d CONNECTION_CLOSE      v = error_code, frame_type (0 for 0x1d); data = the reason
+ *
+ * Known divergence of mq_batch_recv, visible here: in the reference a packet whose frames fail to
+ * decode returns Err from recv_*, so it neither raises largest_recv_pn nor is tracked for ACKs
+ * (recv.rs:231-257). mq_batch_recv knows nothing of frames and has always counted every opened
+ * packet; the caller sees which packets those are by MQ_ERR_FRAME and conn_flags bit 4. */
+#define MQ_ERR_FRAME 10            /* Error::Transport(FrameEncodingError) out of frame::decode       */
+#define MQ_FRAMES_SKIPPED 0xFF     /* mq_pkt_frames.status of a packet whose mq_recv_pkt.status != MQ_OK */
+#define MQ_FRAMES_ACK_ELICITING 0x01  /* mq_pkt_frames.flags (recv.rs:533-539)                          */
+#define MQ_CONN_FRAMES_CLOSE 0x08  /* conn_flags bit 3: a CONNECTION_CLOSE frame was decoded           */
+#define MQ_CONN_FRAMES_ERROR 0x10  /* conn_flags bit 4: some packet got MQ_ERR_FRAME                    */
+
+typedef struct mq_frame {           /* one decoded frame                                          */
+  uint32_t pkt;                     /* index into pkts                                            */
+  uint16_t pos, len;                /* first byte and encoded length, relative to the payload start */
+  uint8_t  type;                    /* the decoded type VALUE, 0x01..0x1e (STREAM keeps its OFF /
+                                       LEN / FIN bits)                                            */
+  uint8_t  level;                   /* copied from the packet                                     */
+  uint16_t data_pos, data_len;      /* the frame's byte string, relative to the payload start     */
+  uint16_t aux;
+  uint64_t v[4];
+} mq_frame;                         /* 48 bytes */
+
+typedef struct mq_pkt_frames {      /* one per packet record                                      */
+  uint32_t first;                   /* index of its first record (valid even beyond max_frames)   */
+  uint16_t n_frames;                /* records of this packet (frames decoded before an error
+                                       included)                                                  */
+  uint16_t err_pos;                 /* MQ_ERR_FRAME: payload position at which the failing decode
+                                       started                                                    */
+  uint16_t n_padding;               /* PADDING frames (= zero type bytes) decoded                 */
+  uint8_t  status;                  /* MQ_OK, MQ_ERR_FRAME, MQ_FRAMES_SKIPPED, MQ_ERR_INVALID_ARG */
+  uint8_t  flags;                   /* MQ_FRAMES_ACK_ELICITING                                    */
+  uint32_t reserved;
+} mq_pkt_frames;                    /* 16 bytes */
+
+/* All pointers are device memory. The packet count is min(*n_pkts_dev, max_pkts), read on the device:
+ * the call chains behind mq_batch_recv (pkts, n_pkts) on one stream with nothing read back. It runs
+ * on the calling thread's device (mq_device_init). summary[i] is written for every packet below the
+ * count (entries beyond it are left alone); a packet whose mq_recv_pkt.status is not MQ_OK gets
+ * MQ_FRAMES_SKIPPED and no records, and none of its bytes is loaded. A packet whose range
+ * [offset, offset + len) leaves the arena, whose payload_offset + 16 exceeds len, or whose payload is
+ * longer than 65535 bytes gets MQ_ERR_INVALID_ARG in its summary, and nothing of it is loaded. No
+ * byte outside a packet's payload is ever loaded.
+ * *n_frames receives the total number of records, which can EXCEED max_frames: only the first
+ * max_frames records, in order, are written; the summaries (first, n_frames) stay complete — the
+ * contract of *n_pkts of mq_batch_recv. The total is a 32-bit sum.
+ * dgrams / n_dgrams, conn_flags / n_conns are optional, given together or not at all: conn_flags[c]
+ * (one word per connection) is zeroed by the call, then bit `level` (0..2) is set by an ack-eliciting
+ * packet of that level that decoded with MQ_OK (ack_eliciting_received, recv.rs:235-237),
+ * MQ_CONN_FRAMES_CLOSE by a decoded CONNECTION_CLOSE frame, MQ_CONN_FRAMES_ERROR by a packet with
+ * MQ_ERR_FRAME. The connection is dgrams[pkts[i].dgram].conn; a dgram index >= n_dgrams or a conn
+ * >= n_conns (MQ_CONN_NONE) is ignored.
+ * The output is a function of the inputs alone. Host-level returns as for mq_batch_route:
+ * MQ_ERR_INVALID_ARG — checked first, nothing launched — for a NULL arena, pkts, n_pkts_dev or
+ * summary with max_pkts > 0, a NULL n_frames or workspace, NULL frames with max_frames > 0, dgrams
+ * without conn_flags or the reverse, max_pkts > 2^24, or pkts / summary / frames / workspace / dgrams
+ * not 16-byte aligned; MQ_OK for max_pkts = 0 (*n_frames = 0, conn_flags zeroed); MQ_ERR_NO_DEVICE /
+ * MQ_ERR_HIP as elsewhere. workspace has mq_batch_frames_workspace_size(max_pkts) bytes; its contents
+ * need not be initialised. */
+size_t mq_batch_frames_workspace_size(uint32_t max_pkts);
+int mq_batch_frames(const uint8_t* arena, uint64_t arena_len, const mq_recv_pkt* pkts,
+                    const uint32_t* n_pkts_dev, uint32_t max_pkts, const mq_dgram* dgrams,
+                    uint32_t n_dgrams, mq_pkt_frames* summary, mq_frame* frames,
+                    uint32_t max_frames, uint32_t* n_frames, uint32_t* conn_flags,
+                    uint32_t n_conns, void* workspace, void* stream);
+
 /* Batched HeaderProtection::mask: masks[i*5..] = mask(key_table[key_ids[i]].hp, samples[i*16..]).
  * An entry whose key id is out of range or whose row holds no valid suite gets an all-zero mask
  * (the call still returns MQ_OK: validate key ids on the caller's side). */

@@ -13,9 +13,10 @@ from .crypto import (Aes128GcmAead, Aes128GcmProvider, AesHeaderProtection, Buff
                      DirectionalKeys, Error, HkdfSha256, InvalidArgument, ProtocolViolation, nonce)
 from . import route  # noqa: F401,E402
 from .route import Admit, CidTable  # noqa: F401,E402
+from . import frames  # noqa: F401,E402
 
 __all__ = [
-    "Admit", "CidTable", "route",
+    "Admit", "CidTable", "route", "frames",
     "Aes128GcmAead", "Aes128GcmProvider", "AesHeaderProtection", "BufferTooSmall", "ChaCha20Poly1305Aead",
     "ChaCha20Provider", "ChaChaHeaderProtection", "CryptoError", "DirectionalKeys", "Error", "HkdfSha256",
     "InvalidArgument", "ProtocolViolation", "nonce",

@@ -27,6 +27,7 @@ MQ_ERR_NO_DEVICE = 6
 MQ_ERR_HIP = 7
 MQ_ERR_TLS = 8
 MQ_ERR_DEFERRED = 9
+MQ_ERR_FRAME = 10
 
 MQ_SUITE_AES128GCM = 1
 MQ_SUITE_CHACHA20 = 2
@@ -49,6 +50,10 @@ MQ_SEND_PAD_TO_MIN = 0x01
 MQ_CONN_NONE = 0xFFFFFFFF
 (MQ_ROUTE_HIT, MQ_ROUTE_NEW, MQ_ROUTE_UNKNOWN, MQ_ROUTE_MALFORMED, MQ_ROUTE_FULL,
  MQ_ROUTE_DEFERRED) = range(6)
+
+MQ_FRAMES_SKIPPED = 0xFF
+MQ_FRAMES_ACK_ELICITING = 0x01
+MQ_CONN_FRAMES_CLOSE, MQ_CONN_FRAMES_ERROR = 0x08, 0x10
 
 
 class KeyMaterial(ctypes.Structure):
@@ -155,6 +160,8 @@ SIGNATURES = {
     "mq_debug_cid_table_hash_bits": (ctypes.c_int, [_vp, _u32]),
     "mq_batch_route_workspace_size": (_sz, [_u32]),
     "mq_batch_route": (ctypes.c_int, [_vp, _vp, _u64, _vp, _u32, _u32, ctypes.POINTER(RouteAdmit), _vp, _vp, _vp]),
+    "mq_batch_frames_workspace_size": (_sz, [_u32]),
+    "mq_batch_frames": (ctypes.c_int, [_vp, _u64, _vp, _vp, _u32, _vp, _u32, _vp, _vp, _u32, _vp, _vp, _u32, _vp, _vp]),
     "mq_keytable_create": (ctypes.c_int, [ctypes.POINTER(KeyMaterial), _u32, ctypes.POINTER(_vp)]),
     "mq_keytable_update": (ctypes.c_int, [_vp, _u32, ctypes.POINTER(KeyMaterial), _u32]),
     "mq_keytable_rows": (_u32, [_vp]),

@@ -614,6 +614,7 @@ const char* mq_status_str(int status) {
     case MQ_ERR_NO_DEVICE: return "no gfx950 device";
     case MQ_ERR_HIP: return "hip runtime error";
     case MQ_ERR_TLS: return "tls";
+    case MQ_ERR_FRAME: return "frame encoding";
     default: return "unknown";
   }
 }
@@ -1384,6 +1385,35 @@ int mq_batch_route(mq_cid_table* t, const uint8_t* arena, uint64_t arena_len, mq
   if (n_dgrams == 0 && !admit) return MQ_OK;
   return mq_launch_route(t->d, arena, arena_len, dgrams, n_dgrams, short_dcid_len, admit, status, workspace,
                          (hipStream_t)stream) == hipSuccess
+             ? MQ_OK
+             : MQ_ERR_HIP;
+}
+
+// ---- frame index behind mq_batch_recv (mq_frames.hip) ------------------------------------------
+size_t mq_batch_frames_workspace_size(uint32_t max_pkts) { return mq_frames_workspace(max_pkts); }
+
+int mq_batch_frames(const uint8_t* arena, uint64_t arena_len, const mq_recv_pkt* pkts, const uint32_t* n_pkts_dev,
+                    uint32_t max_pkts, const mq_dgram* dgrams, uint32_t n_dgrams, mq_pkt_frames* summary,
+                    mq_frame* frames, uint32_t max_frames, uint32_t* n_frames, uint32_t* conn_flags, uint32_t n_conns,
+                    void* workspace, void* stream) {
+  if (max_pkts > (1u << 24) || !n_frames || !workspace || (max_frames && !frames)) return MQ_ERR_INVALID_ARG;
+  if (max_pkts && (!arena || !pkts || !n_pkts_dev || !summary)) return MQ_ERR_INVALID_ARG;
+  if ((dgrams != nullptr) != (conn_flags != nullptr)) return MQ_ERR_INVALID_ARG;
+  if ((((uintptr_t)pkts | (uintptr_t)summary | (uintptr_t)frames | (uintptr_t)workspace | (uintptr_t)dgrams) & 15) != 0)
+    return MQ_ERR_INVALID_ARG;
+  const int dev = creation_device();
+  if (dev < 0) return MQ_ERR_NO_DEVICE;
+  DeviceGuard g(dev);
+  if (!g.ok()) return MQ_ERR_NO_DEVICE;
+  hipStream_t s = (hipStream_t)stream;
+  if (max_pkts == 0) {
+    if (hipMemsetAsync(n_frames, 0, 4, s) != hipSuccess) return MQ_ERR_HIP;
+    if (conn_flags && n_conns && hipMemsetAsync(conn_flags, 0, 4 * (size_t)n_conns, s) != hipSuccess)
+      return MQ_ERR_HIP;
+    return MQ_OK;
+  }
+  return mq_launch_frames(arena, arena_len, pkts, n_pkts_dev, max_pkts, dgrams, n_dgrams, summary, frames, max_frames,
+                          n_frames, conn_flags, n_conns, workspace, s) == hipSuccess
              ? MQ_OK
              : MQ_ERR_HIP;
 }

@@ -138,6 +138,13 @@ hipError_t mq_launch_cid_compact(const mq::CidTableDev& t, void* to, hipStream_t
 int mq_resident_call(int dev, const mq::ResReq& q, uint64_t uid, const uint8_t* aad, const uint8_t* body, uint8_t* out,
                      size_t out_off, size_t out_len, int* status, uint32_t* mask);
 
+// ---- mq_frames.hip ------------------------------------------------------------------------------
+size_t mq_frames_workspace(uint32_t max_pkts);
+hipError_t mq_launch_frames(const uint8_t* arena, uint64_t arena_len, const mq_recv_pkt* pkts,
+                            const uint32_t* n_pkts_dev, uint32_t max_pkts, const mq_dgram* dgrams, uint32_t n_dgrams,
+                            mq_pkt_frames* summary, mq_frame* frames, uint32_t max_frames, uint32_t* n_frames,
+                            uint32_t* conn_flags, uint32_t n_conns, void* workspace, hipStream_t s);
+
 #ifdef MQ_STAMPS
 void mq_stamps_set_chacha(uint64_t* p);
 void mq_stamps_set_aes(uint64_t* p);

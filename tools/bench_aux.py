@@ -16,7 +16,11 @@ stream; median of `reps`). Prints one JSON object; the round's copy lives in pro
            mq_batch_recv over the same batch), all hits over 2^20 connections (a 64-MiB table), and an
            Initial flood of 2^20 distinct new DCIDs with max_new = 2^20 (with mq_batch_derive_initial
            over what it admitted); 4096 datagrams of each run checked against tests/route_model.py
-Usage: python tools/bench_aux.py [reps] | rekey [reps] | recv reps conns... | route [reps]
+  frames   mq_batch_frames over 2^20 opened packets (its own mode only): the recv mode's 1200-B 1-RTT
+           batch with frame streams of an ACK, three control frames and a STREAM frame to the end, behind
+           mq_batch_recv of the same run, and an Initial-shaped plaintext batch (a 300-B CRYPTO frame, the
+           rest PADDING); 4096 packets of each checked against tests/frames_model.py
+Usage: python tools/bench_aux.py [reps] | rekey [reps] | recv reps conns... | route [reps] | frames [reps]
 """
 import json
 import os
@@ -370,7 +374,120 @@ def bench_route(reps, n=1 << 20, L=1200, k=4096):
     return res
 
 
+def frames_sample_check(arena, pkts, summ, rec, idx, L):
+    """Packets idx of a timed mq_batch_frames run against the Python model (tests/frames_model.py),
+    which gets their bytes: every summary field but `first`, and every record."""
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
+    import frames_model
+    rows = arena.view(-1, L)[torch.from_numpy(idx.astype(np.int64)).to(DEV)].cpu().numpy()
+    sub = pkts[idx].copy()
+    sub["offset"] = np.arange(len(idx), dtype=np.uint64) * np.uint64(L)
+    w_summ, w_rec, _ = frames_model.run(rows.reshape(-1), sub, len(idx))
+    for f in ("n_frames", "err_pos", "n_padding", "status", "flags"):
+        assert (summ[f][idx] == w_summ[f]).all(), f"frames sample: summary {f} differs from the model"
+    got = np.concatenate([rec[int(summ["first"][g]):int(summ["first"][g]) + int(summ["n_frames"][g])] for g in idx])
+    assert len(got) == len(w_rec) and (got["pkt"] == idx[w_rec["pkt"]]).all()
+    for f in ("pos", "len", "type", "level", "data_pos", "data_len", "aux", "v"):
+        assert (got[f] == w_rec[f]).all(), f"frames sample: record {f} differs from the model"
+    return len(idx)
+
+
+def bench_frames(reps, n=1 << 20, n_conns=4096, L=1200, k=4096):
+    """mq_batch_frames behind mq_batch_recv over 2^20 opened packets: the `recv` mode's 1-RTT batch
+    with real frame streams, and an Initial-shaped plaintext batch (a CRYPTO frame, the rest PADDING)."""
+    from milli_quic_amd import frames as fr
+    fl = 1171
+    i = np.arange(n, dtype=np.uint64)
+    pick = np.sort(np.random.default_rng(12).choice(n, size=k, replace=False))
+    # ---- 1-RTT: ACK (one extra range), MAX_DATA, MAX_STREAM_DATA, PING, STREAM (OFF, no LEN) to the end
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
+    from frames_model import build, vi
+    head = (build(0x02, (0x0FFFFFF0, 250, 1, 3, 1, 2)) + build(0x10, (1 << 24,)) + build(0x11, (4, 1 << 20)) + b"\x01"
+            + b"\x0c" + vi(4) + vi(1 << 31))
+    fs = workload.splitmix_bytes(n * fl, seed=3).reshape(n, fl)
+    fs[:, :len(head)] = np.frombuffer(head, dtype=np.uint8)
+    fs[:, 6] = (i & np.uint64(0xFF)).astype(np.uint8)  # the ACK delay's low byte differs per packet
+    w = workload.uniform(64, _lib.MQ_SUITE_CHACHA20, n_keys=n_conns)
+    kt = KeyTable(w.keys)
+    conns = send.make_conns([workload.DCID8] * n_conns, [b""] * n_conns, [[c, c, c] for c in range(n_conns)])
+    req = np.zeros(n, dtype=send.REQ_DTYPE)
+    req["frames_offset"], req["out_offset"] = i * np.uint64(fl), i * np.uint64(L)
+    req["pn"] = np.uint64(0x10000000) + i // np.uint64(n_conns)
+    req["largest_acked"] = req["pn"] - np.uint64(1 << 24)
+    req["frame_len"], req["out_cap"], req["level"] = fl, L, send.APPLICATION
+    req["conn"] = (i % np.uint64(n_conns)).astype(np.uint32)
+    fs_d = t(fs)
+    del fs
+    out = torch.zeros(n * L, dtype=torch.uint8, device=DEV)
+    st = torch.zeros(n, dtype=torch.uint8, device=DEV)
+    ln = torch.zeros(n, dtype=torch.int32, device=DEV)
+    ws = torch.empty(send.workspace_bytes(n), dtype=torch.uint8, device=DEV)
+    send.protect(kt, t(conns), fs_d, out, t(req), st, ln, _lib.MQ_SUITE_CHACHA20, ws)
+    torch.cuda.synchronize()
+    assert int((st != 0).sum()) == 0
+    del fs_d, ws
+    sealed = out.clone()
+    rc = np.zeros(n_conns, dtype=recv.CONN_DTYPE)
+    rc["app_row"][:, 1] = np.arange(n_conns)
+    rc["dcid_len"], rc["flags"] = 8, recv.HAS_APP
+    dg = np.zeros(n, dtype=recv.DGRAM_DTYPE)
+    dg["offset"], dg["len"], dg["conn"] = i * np.uint64(L), L, req["conn"]
+    dgt = t(dg)
+    pk = torch.zeros(n * 32, dtype=torch.uint8, device=DEV)
+    cnt = torch.zeros(1, dtype=torch.int32, device=DEV)
+    rws = torch.empty(recv.workspace_bytes(n, n, n_conns), dtype=torch.uint8, device=DEV)
+    ct0 = t(rc)
+    ct = ct0.clone()
+    copy_ms = timed(lambda: (out.copy_(sealed), ct.copy_(ct0)), reps)
+    ms_r = timed(lambda: (out.copy_(sealed), ct.copy_(ct0), recv.recv(kt, ct, out, dgt, pk, cnt, rws)), reps) - copy_ms
+    assert int(cnt[0]) == n and (pk.cpu().numpy().view(recv.PKT_DTYPE)["status"] == 0).all()
+    del sealed, rws
+    max_frames = 5 * n
+    summ = torch.zeros(n * 16, dtype=torch.uint8, device=DEV)
+    rec = torch.zeros(max_frames * 48, dtype=torch.uint8, device=DEV)
+    total = torch.zeros(1, dtype=torch.int32, device=DEV)
+    cf = torch.zeros(n_conns, dtype=torch.int32, device=DEV)
+    fws = torch.empty(fr.workspace_bytes(n), dtype=torch.uint8, device=DEV)
+    ms_f = timed(lambda: fr.scan(out, pk, cnt, summ, rec, total, fws, dgrams=dgt, conn_flags=cf), reps)
+    h_summ = summ.cpu().numpy().view(fr.PKT_FRAMES_DTYPE)
+    assert int(total[0]) == 5 * n and (h_summ["status"] == 0).all() and (h_summ["n_frames"] == 5).all()
+    assert int((cf != 4).sum()) == 0  # every connection: an ack-eliciting 1-RTT packet
+    checked = frames_sample_check(out, pk.cpu().numpy().view(recv.PKT_DTYPE), h_summ,
+                                  rec.cpu().numpy().view(fr.FRAME_DTYPE), pick, L)
+    res = {"one_rtt": {"packets": n, "records": 5 * n, "frames_ms": round(ms_f, 4), "recv_ms": round(ms_r, 4),
+                       "frames_over_recv": round(ms_f / ms_r, 4), "Mpkts_per_s": round(n / ms_f / 1e3, 1),
+                       "sample_checked": checked}}
+    # ---- Initial-shaped: 22 header bytes, CRYPTO (offset 0, 300 bytes), PADDING up to the tag; plaintext, with
+    # ---- fabricated packet records (the scan reads nothing else)
+    po = 22
+    crypto = build(0x06, (0, 300))
+    rows = out.view(n, L)
+    rows.zero_()
+    rows[:, :po] = 0xC3
+    rows[:, po:po + len(crypto)] = t(np.frombuffer(crypto, dtype=np.uint8))
+    rows[:, po + len(crypto):po + len(crypto) + 300] = 0x5C
+    rows[:, L - 16:] = 0xEE
+    pkts = np.zeros(n, dtype=recv.PKT_DTYPE)
+    pkts["offset"], pkts["len"], pkts["dgram"], pkts["payload_offset"] = i * np.uint64(L), L, i.astype(np.uint32), po
+    pk.copy_(t(pkts))
+    ms_i = timed(lambda: fr.scan(out, pk, cnt, summ, rec, total, fws, dgrams=dgt, conn_flags=cf), reps)
+    h_summ = summ.cpu().numpy().view(fr.PKT_FRAMES_DTYPE)
+    assert int(total[0]) == n and (h_summ["status"] == 0).all() and (h_summ["n_frames"] == 1).all()
+    assert (h_summ["n_padding"] == L - 16 - po - len(crypto) - 300).all() and int((cf != 1).sum()) == 0
+    checked = frames_sample_check(out, pkts, h_summ, rec.cpu().numpy().view(fr.FRAME_DTYPE), pick, L)
+    res["initial_shaped"] = {"packets": n, "records": n, "padding_bytes_per_packet": L - 16 - po - len(crypto) - 300,
+                             "frames_ms": round(ms_i, 4), "recv_ms_one_rtt": round(ms_r, 4),
+                             "frames_over_recv": round(ms_i / ms_r, 4), "Mpkts_per_s": round(n / ms_i / 1e3, 1),
+                             "sample_checked": checked}
+    return res
+
+
 def main():
+    if len(sys.argv) > 1 and sys.argv[1] == "frames":  # frame index runs only: frames [REPS]
+        assert _lib.load().mq_device_init(0) == 0
+        reps = int(sys.argv[2]) if len(sys.argv) > 2 else 5
+        print(json.dumps({"device": torch.cuda.get_device_name(0), "frames": bench_frames(reps)}), flush=True)
+        return
     if len(sys.argv) > 1 and sys.argv[1] == "route":  # routing runs only: route [REPS]
         assert _lib.load().mq_device_init(0) == 0
         reps = int(sys.argv[2]) if len(sys.argv) > 2 else 5
