@@ -597,10 +597,12 @@ int mq_batch_route(mq_cid_table* t, const uint8_t* arena, uint64_t arena_len, mq
  *   0x1a/0x1b PATH_*                data = the 8 bytes
  *   0x1c/0x1d CONNECTION_CLOSE      v = error_code, frame_type (0 for 0x1d); data = the reason
  *
- * Known divergence of mq_batch_recv, visible here: in the reference a packet whose frames fail to
- * decode returns Err from recv_*, so it neither raises largest_recv_pn nor is tracked for ACKs
- * (recv.rs:231-257). mq_batch_recv knows nothing of frames and has always counted every opened
- * packet; the caller sees which packets those are by MQ_ERR_FRAME and conn_flags bit 4. */
+ * Where mq_batch_recv differs, visible here: in the reference a packet whose frames fail to decode
+ * returns Err from recv_*, so it neither raises largest_recv_pn nor is tracked for ACKs
+ * (recv.rs:231-257). mq_batch_recv knows nothing of frames and counts every opened packet in
+ * largest_pn; the caller sees which packets those are by MQ_ERR_FRAME and conn_flags bit 4. The
+ * tracking half is resolved in mq_batch_acks below, which sees the summaries and records no such
+ * packet. */
 #define MQ_ERR_FRAME 10            /* Error::Transport(FrameEncodingError) out of frame::decode       */
 #define MQ_FRAMES_SKIPPED 0xFF     /* mq_pkt_frames.status of a packet whose mq_recv_pkt.status != MQ_OK */
 #define MQ_FRAMES_ACK_ELICITING 0x01  /* mq_pkt_frames.flags (recv.rs:533-539)                          */
@@ -660,6 +662,87 @@ int mq_batch_frames(const uint8_t* arena, uint64_t arena_len, const mq_recv_pkt*
                     uint32_t n_dgrams, mq_pkt_frames* summary, mq_frame* frames,
                     uint32_t max_frames, uint32_t* n_frames, uint32_t* conn_flags,
                     uint32_t n_conns, void* workspace, void* stream);
+
+/* ---- ACKs: received-PN trackers and ACK frames behind the frame index (mq_batch_acks) -------------
+ * The per-packet work between the receive and the send side: every opened packet's number is
+ * recorded per packet-number space (track_received_pn -> RecvPnTracker::record,
+ * src/connection/recv.rs:248-249, src/connection/mod.rs:194-296, 855-858), and a tracker whose level
+ * has seen an ack-eliciting packet is turned into an ACK frame (build_ack_frame,
+ * src/connection/transmit.rs:321-380, encoded as src/frame/mod.rs:482-508) that goes out as a packet
+ * of its own through mq_batch_protect:   recv -> frames -> acks -> protect, on one stream.
+ *
+ * Tracker. One RecvPnTracker per (connection, level), trackers[3 * conn + level], in the reference's
+ * default form (no `alloc`, Cargo.toml:9): heapless::Vec<(u64, u64), 32>, at most 32 inclusive ranges,
+ * ascending, non-overlapping and non-adjacent. record(pn) is mod.rs:224-278: a PN inside a range is a
+ * no-op; otherwise it extends a range upward, extends one downward or bridges two into one; otherwise
+ * it becomes a range of its own, and if 32 ranges are in use THE LOWEST RANGE IS REMOVED FIRST, even
+ * when the new PN lies below every range (it then becomes the new lowest). Once the cap is reached
+ * the result depends on arrival order: the call's result equals the sequential replay in the order
+ * of pkts, not "the top 32 ranges of the set". Packet numbers are below 2^62.
+ *
+ * Recorded are, in the order of pkts, the packets with pkts[i].status == MQ_OK, level < 3,
+ * pkts[i].dgram < n_dgrams, dgrams[..].conn < n_conns and, if summary is given, summary[i].status ==
+ * MQ_OK: a packet with MQ_ERR_FRAME or MQ_ERR_INVALID_ARG is not recorded (recv.rs:231-257). With
+ * summary == NULL every opened packet is recorded (mq_batch_recv's own view).
+ *
+ * Pending bits. ack_pending[c], one word per connection, in/out: bits 0..2 are the reference's
+ * ack_eliciting_received[level]. The call ORs in conn_flags[c] & 7 when conn_flags (the output of
+ * mq_batch_frames) is given. The state persists across calls, as the reference's does.
+ *
+ * Build (build != NULL), after tracking, so that an ACK covers the batch's own packets: for every
+ * (c, level), ascending, whose pending bit is set and whose tracker is not empty, one ACK frame: type
+ * 0x02, largest_ack = the end of the top range, ack_delay 0, ack_range_count = n - 1, first_ack_range,
+ * then from the next-highest range down gap = prev_start - end - 2 and range = end - start, every
+ * value a shortest-form varint. The reference's 512-byte range buffer cannot overflow (31 pairs take
+ * at most 496 bytes); the largest frame has 515 bytes. The pending bit is cleared when the frame is
+ * built (transmit.rs:169-173, 237-241, 286-290); with an empty tracker it stays set (build_ack_frame
+ * returns None). ACK k, the k-th due in (conn, level) order, has its frame at ack_frames + 528 k and
+ * reqs[k] = { frames_offset = 528 k, out_offset = k * out_stride, pn = next_pn[3c + l] (then
+ * incremented; transmit.rs:634, 740), largest_acked = conns[c].largest_pn[l] (:509, 635), frame_len,
+ * out_cap = out_stride, conn, level, flags = MQ_SEND_PAD_TO_MIN for an Initial under MQ_ACKS_CLIENT
+ * (:188), else 0 }. *n_acks receives the number of ACKs due, which can EXCEED max_acks (the contract
+ * of *n_frames): those beyond max_acks are not built, keep their pending bit and their next_pn, and
+ * the next call builds them. Requests [min(*n_acks, max_acks), max_acks) are written as null requests
+ * (conn = MQ_CONN_NONE, everything else 0), so mq_batch_protect(n = max_acks) can run behind the call
+ * with nothing read back: it answers MQ_ERR_INVALID_ARG for them and writes nothing. */
+#define MQ_PN_TRACKER_RANGES 32
+#define MQ_ACK_FRAME_MAX 528
+#define MQ_ACKS_CLIENT 0x01         /* ACK-only Initial requests get MQ_SEND_PAD_TO_MIN (transmit.rs:188) */
+
+typedef struct mq_pn_tracker {      /* one RecvPnTracker; all-zero = empty. trackers[3 * conn + level] */
+  uint32_t n;                       /* ranges in use, 0..32 */
+  uint32_t reserved[3];
+  uint64_t range[32][2];            /* (start, end) inclusive, ascending, non-adjacent */
+} mq_pn_tracker;                    /* 528 bytes */
+
+typedef struct mq_ack_build {       /* NULL = track only */
+  uint8_t*  ack_frames;             /* MQ_ACK_FRAME_MAX * max_acks bytes: ack k at 528 * k */
+  mq_send_req* reqs;                /* max_acks requests for mq_batch_protect */
+  uint32_t* n_acks;                 /* device: ACKs due, can EXCEED max_acks */
+  const mq_conn_recv* conns;        /* largest_pn[level] -> req.largest_acked (transmit.rs:509, 635) */
+  uint64_t* next_pn;                /* [3 * n_conns] in/out: req.pn, then + 1 (transmit.rs:634, 740) */
+  uint32_t  max_acks, out_stride, flags, reserved;
+} mq_ack_build;                     /* 56 bytes */
+
+/* All pointers are device memory, except `build` itself, a host struct of device pointers. The packet
+ * count is min(*n_pkts_dev, max_pkts), read on the device. summary, conn_flags and build are optional.
+ * A tracker that receives no packet in the call is left as it is; one that does is written back
+ * whole: n (a loaded n above 32 is clamped to 32), its ranges, and zeros in the unused ranges; the
+ * reserved words are never written. Whatever the tables hold, nothing outside a tracker's 528 bytes
+ * and the stated outputs is read or written; bytes of a frame slot behind frame_len are left alone.
+ * The output is a function of the inputs alone. Host-level returns as for mq_batch_frames:
+ * MQ_ERR_INVALID_ARG — checked first, nothing launched — for a NULL pkts, n_pkts_dev, dgrams, trackers
+ * or ack_pending with max_pkts > 0 and n_conns > 0 (trackers and ack_pending also with max_pkts = 0), a
+ * NULL workspace, max_pkts > 2^24, n_conns > 2^30, a build with max_acks > 0 and a NULL member pointer
+ * or out_stride == 0 (n_acks must never be NULL), or pkts / summary / dgrams / trackers / workspace /
+ * reqs / conns not 16-byte aligned; MQ_OK for max_pkts == 0 (the build half still runs on the pending
+ * bits); MQ_ERR_NO_DEVICE / MQ_ERR_HIP as elsewhere. workspace has
+ * mq_batch_acks_workspace_size(max_pkts, n_conns) bytes; its contents need not be initialised. */
+size_t mq_batch_acks_workspace_size(uint32_t max_pkts, uint32_t n_conns);
+int mq_batch_acks(const mq_recv_pkt* pkts, const uint32_t* n_pkts_dev, uint32_t max_pkts,
+                  const mq_pkt_frames* summary, const mq_dgram* dgrams, uint32_t n_dgrams,
+                  const uint32_t* conn_flags, mq_pn_tracker* trackers, uint32_t* ack_pending,
+                  uint32_t n_conns, const mq_ack_build* build, void* workspace, void* stream);
 
 /* Batched HeaderProtection::mask: masks[i*5..] = mask(key_table[key_ids[i]].hp, samples[i*16..]).
  * An entry whose key id is out of range or whose row holds no valid suite gets an all-zero mask

@@ -55,6 +55,10 @@ MQ_FRAMES_SKIPPED = 0xFF
 MQ_FRAMES_ACK_ELICITING = 0x01
 MQ_CONN_FRAMES_CLOSE, MQ_CONN_FRAMES_ERROR = 0x08, 0x10
 
+MQ_PN_TRACKER_RANGES = 32
+MQ_ACK_FRAME_MAX = 528
+MQ_ACKS_CLIENT = 0x01
+
 
 class KeyMaterial(ctypes.Structure):
     """mq_key_material: what CryptoProvider::aead + ::header_protection consume."""
@@ -105,6 +109,22 @@ assert ctypes.sizeof(PktDesc) == 32
 assert ctypes.sizeof(RouteAdmit) == 56
 
 _u8p = ctypes.POINTER(ctypes.c_uint8)
+class AckBuild(ctypes.Structure):
+    """mq_ack_build: where mq_batch_acks puts ACK frames and their send requests (device pointers)."""
+
+    _fields_ = [
+        ("ack_frames", ctypes.c_void_p),
+        ("reqs", ctypes.c_void_p),
+        ("n_acks", ctypes.c_void_p),
+        ("conns", ctypes.c_void_p),
+        ("next_pn", ctypes.c_void_p),
+        ("max_acks", ctypes.c_uint32),
+        ("out_stride", ctypes.c_uint32),
+        ("flags", ctypes.c_uint32),
+        ("reserved", ctypes.c_uint32),
+    ]
+
+
 _vp = ctypes.c_void_p
 _sz = ctypes.c_size_t
 _u32 = ctypes.c_uint32
@@ -162,6 +182,8 @@ SIGNATURES = {
     "mq_batch_route": (ctypes.c_int, [_vp, _vp, _u64, _vp, _u32, _u32, ctypes.POINTER(RouteAdmit), _vp, _vp, _vp]),
     "mq_batch_frames_workspace_size": (_sz, [_u32]),
     "mq_batch_frames": (ctypes.c_int, [_vp, _u64, _vp, _vp, _u32, _vp, _u32, _vp, _vp, _u32, _vp, _vp, _u32, _vp, _vp]),
+    "mq_batch_acks_workspace_size": (_sz, [_u32, _u32]),
+    "mq_batch_acks": (ctypes.c_int, [_vp, _vp, _u32, _vp, _vp, _u32, _vp, _vp, _vp, _u32, ctypes.POINTER(AckBuild), _vp, _vp]),
     "mq_keytable_create": (ctypes.c_int, [ctypes.POINTER(KeyMaterial), _u32, ctypes.POINTER(_vp)]),
     "mq_keytable_update": (ctypes.c_int, [_vp, _u32, ctypes.POINTER(KeyMaterial), _u32]),
     "mq_keytable_rows": (_u32, [_vp]),

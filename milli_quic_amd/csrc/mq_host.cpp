@@ -1418,6 +1418,34 @@ int mq_batch_frames(const uint8_t* arena, uint64_t arena_len, const mq_recv_pkt*
              : MQ_ERR_HIP;
 }
 
+// ---- received-PN trackers and ACK frames behind mq_batch_frames (mq_acks.hip) -------------------
+size_t mq_batch_acks_workspace_size(uint32_t max_pkts, uint32_t n_conns) { return mq_acks_workspace(max_pkts, n_conns); }
+
+int mq_batch_acks(const mq_recv_pkt* pkts, const uint32_t* n_pkts_dev, uint32_t max_pkts, const mq_pkt_frames* summary,
+                  const mq_dgram* dgrams, uint32_t n_dgrams, const uint32_t* conn_flags, mq_pn_tracker* trackers,
+                  uint32_t* ack_pending, uint32_t n_conns, const mq_ack_build* build, void* workspace, void* stream) {
+  if (max_pkts > (1u << 24) || n_conns > (1u << 30) || !workspace) return MQ_ERR_INVALID_ARG;
+  if (max_pkts && n_conns && (!pkts || !n_pkts_dev || !dgrams)) return MQ_ERR_INVALID_ARG;
+  if (n_conns && (!trackers || !ack_pending)) return MQ_ERR_INVALID_ARG;
+  uintptr_t align = (uintptr_t)pkts | (uintptr_t)summary | (uintptr_t)dgrams | (uintptr_t)trackers | (uintptr_t)workspace;
+  if (build) {
+    if (!build->n_acks) return MQ_ERR_INVALID_ARG;
+    if (build->max_acks &&
+        (!build->ack_frames || !build->reqs || !build->conns || !build->next_pn || build->out_stride == 0))
+      return MQ_ERR_INVALID_ARG;
+    align |= (uintptr_t)build->reqs | (uintptr_t)build->conns;
+  }
+  if ((align & 15) != 0) return MQ_ERR_INVALID_ARG;
+  const int dev = creation_device();
+  if (dev < 0) return MQ_ERR_NO_DEVICE;
+  DeviceGuard g(dev);
+  if (!g.ok()) return MQ_ERR_NO_DEVICE;
+  return mq_launch_acks(pkts, n_pkts_dev, max_pkts, summary, dgrams, n_dgrams, conn_flags, trackers, ack_pending,
+                        n_conns, build, workspace, (hipStream_t)stream) == hipSuccess
+             ? MQ_OK
+             : MQ_ERR_HIP;
+}
+
 // ---- TLS 1.3 records (tcp_tls/record.rs:88-143, connection.rs:546-600) -----------------------
 int mq_record_seal(const mq_aead_ctx* ctx, const uint8_t* nonce, size_t nonce_len, uint8_t* buf,
                    size_t buf_len, size_t payload_len, uint8_t inner_type, size_t* out_len,

@@ -145,6 +145,13 @@ hipError_t mq_launch_frames(const uint8_t* arena, uint64_t arena_len, const mq_r
                             mq_pkt_frames* summary, mq_frame* frames, uint32_t max_frames, uint32_t* n_frames,
                             uint32_t* conn_flags, uint32_t n_conns, void* workspace, hipStream_t s);
 
+// ---- mq_acks.hip --------------------------------------------------------------------------------
+size_t mq_acks_workspace(uint32_t max_pkts, uint32_t n_conns);
+hipError_t mq_launch_acks(const mq_recv_pkt* pkts, const uint32_t* n_pkts_dev, uint32_t max_pkts,
+                          const mq_pkt_frames* summary, const mq_dgram* dgrams, uint32_t n_dgrams,
+                          const uint32_t* conn_flags, mq_pn_tracker* trackers, uint32_t* ack_pending, uint32_t n_conns,
+                          const mq_ack_build* build, void* workspace, hipStream_t s);
+
 #ifdef MQ_STAMPS
 void mq_stamps_set_chacha(uint64_t* p);
 void mq_stamps_set_aes(uint64_t* p);

@@ -20,7 +20,12 @@ stream; median of `reps`). Prints one JSON object; the round's copy lives in pro
            batch with frame streams of an ACK, three control frames and a STREAM frame to the end, behind
            mq_batch_recv of the same run, and an Initial-shaped plaintext batch (a 300-B CRYPTO frame, the
            rest PADDING); 4096 packets of each checked against tests/frames_model.py
-Usage: python tools/bench_aux.py [reps] | rekey [reps] | recv reps conns... | route [reps] | frames [reps]
+  acks     mq_batch_acks (track + build) over 2^20 opened packets (its own mode only): the frames mode's
+           1-RTT batch behind mq_batch_recv and mq_batch_frames of the same run, over 4096, 64 and 1
+           connections in order and over 4096 connections with loss and reordering (gaps of 2..300 with
+           p = 0.02, ~40000 with p = 0.001, adjacent packets swapped with p = 0.01); every timed call
+           starts from empty trackers; a sample of connections checked against tests/acks_model.py
+Usage: python tools/bench_aux.py [reps] | rekey [reps] | recv reps conns... | route [reps] | frames [reps] | acks [reps [batch]]
 """
 import json
 import os
@@ -40,7 +45,8 @@ def t(a):
     return torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).reshape(-1).copy()).to(DEV)
 
 
-def timed(fn, reps):
+def timed_all(fn, reps):
+    """One warm-up call, then `reps` timed ones: (median, min, max) in ms."""
     out = []
     for _ in range(reps + 1):
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -49,7 +55,11 @@ def timed(fn, reps):
         e1.record()
         torch.cuda.synchronize()
         out.append(e0.elapsed_time(e1))
-    return float(np.median(out[1:]))
+    return float(np.median(out[1:])), float(min(out[1:])), float(max(out[1:]))
+
+
+def timed(fn, reps):
+    return timed_all(fn, reps)[0]
 
 
 def bench_derive(reps, n=1 << 20):
@@ -482,7 +492,134 @@ def bench_frames(reps, n=1 << 20, n_conns=4096, L=1200, k=4096):
     return res
 
 
+def acks_pns(n, n_conns, lossy, seed=7):
+    """Packet i belongs to connection i % n_conns and is its (i // n_conns)-th arrival. In order: PNs
+    step by 1. Lossy: gaps of 2..300 (p = 0.02) and of ~40000 (p = 0.001), adjacent arrivals swapped
+    (p = 0.01), per connection."""
+    per = n // n_conns
+    if not lossy:
+        return (np.uint64(0x10000000) + np.arange(n, dtype=np.uint64) // np.uint64(n_conns))
+    rng = np.random.default_rng(seed)
+    inc = np.ones((n_conns, per), dtype=np.int64)
+    u = rng.random((n_conns, per))
+    inc[u < 0.02] = rng.integers(2, 300, size=int((u < 0.02).sum()))
+    inc[u < 0.001] = 40000 + rng.integers(0, 1000, size=int((u < 0.001).sum()))
+    pns = np.cumsum(inc, axis=1) + 0x10000000
+    swap = np.nonzero(rng.random((n_conns, per // 2)) < 0.02)   # pairs (2k, 2k + 1): 0.01 per packet
+    a, b = pns[swap[0], 2 * swap[1]].copy(), pns[swap[0], 2 * swap[1] + 1].copy()
+    pns[swap[0], 2 * swap[1]], pns[swap[0], 2 * swap[1] + 1] = b, a
+    return np.ascontiguousarray(pns.T).reshape(-1).astype(np.uint64)
+
+
+def bench_acks(reps, n=1 << 20, L=1200, k=12, only=None):
+    """recv -> frames -> acks over 2^20 1-RTT packets, each step timed on the same batch; `only` names the
+    one batch to run (profiler runs)."""
+    from milli_quic_amd import acks as ak, frames as fr
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
+    import acks_model as am
+    from frames_model import build, vi
+    fl = 1171
+    i = np.arange(n, dtype=np.uint64)
+    head = (build(0x02, (0x0FFFFFF0, 250, 1, 3, 1, 2)) + build(0x10, (1 << 24,)) + build(0x11, (4, 1 << 20)) + b"\x01"
+            + b"\x0c" + vi(4) + vi(1 << 31))
+    fs = workload.splitmix_bytes(n * fl, seed=3).reshape(n, fl)
+    fs[:, :len(head)] = np.frombuffer(head, dtype=np.uint8)
+    fs_d = t(fs)
+    del fs
+    out = torch.zeros(n * L, dtype=torch.uint8, device=DEV)
+    sealed = torch.zeros(n * L, dtype=torch.uint8, device=DEV)
+    res = {}
+    for name, n_conns, lossy in (("in_order_4096", 4096, False), ("in_order_64", 64, False), ("in_order_1", 1, False),
+                                 ("lossy_4096", 4096, True)):
+        if only is not None and name != only:
+            continue
+        w = workload.uniform(64, _lib.MQ_SUITE_CHACHA20, n_keys=n_conns)
+        kt = KeyTable(w.keys)
+        conns = send.make_conns([workload.DCID8] * n_conns, [b""] * n_conns, [[c, c, c] for c in range(n_conns)])
+        pns = acks_pns(n, n_conns, lossy)
+        req = np.zeros(n, dtype=send.REQ_DTYPE)
+        req["frames_offset"], req["out_offset"] = i * np.uint64(fl), i * np.uint64(L)
+        req["pn"] = pns
+        req["largest_acked"] = pns - np.uint64(1 << 24)
+        req["frame_len"], req["out_cap"], req["level"] = fl, L, send.APPLICATION
+        req["conn"] = (i % np.uint64(n_conns)).astype(np.uint32)
+        st = torch.zeros(n, dtype=torch.uint8, device=DEV)
+        ln = torch.zeros(n, dtype=torch.int32, device=DEV)
+        ws = torch.empty(send.workspace_bytes(n), dtype=torch.uint8, device=DEV)
+        send.protect(kt, t(conns), fs_d, out, t(req), st, ln, _lib.MQ_SUITE_CHACHA20, ws)
+        torch.cuda.synchronize()
+        assert int((st != 0).sum()) == 0
+        del ws
+        sealed.copy_(out)
+        rc = np.zeros(n_conns, dtype=recv.CONN_DTYPE)
+        rc["app_row"][:, 1] = np.arange(n_conns)
+        rc["dcid_len"], rc["flags"] = 8, recv.HAS_APP
+        dg = np.zeros(n, dtype=recv.DGRAM_DTYPE)
+        dg["offset"], dg["len"], dg["conn"] = i * np.uint64(L), L, req["conn"]
+        dgt = t(dg)
+        pk = torch.zeros(n * 32, dtype=torch.uint8, device=DEV)
+        cnt = torch.zeros(1, dtype=torch.int32, device=DEV)
+        rws = torch.empty(recv.workspace_bytes(n, n, n_conns), dtype=torch.uint8, device=DEV)
+        ct0 = t(rc)
+        ct = ct0.clone()
+        copy_ms = timed(lambda: (out.copy_(sealed), ct.copy_(ct0)), reps)
+        r_ms = [x - copy_ms for x in timed_all(lambda: (out.copy_(sealed), ct.copy_(ct0),
+                                                       recv.recv(kt, ct, out, dgt, pk, cnt, rws)), reps)]
+        h_pk = pk.cpu().numpy().view(recv.PKT_DTYPE)
+        assert int(cnt[0]) == n and (h_pk["status"] == 0).all() and (h_pk["pn"] == pns).all()
+        del rws
+        summ = torch.zeros(n * 16, dtype=torch.uint8, device=DEV)
+        rec = torch.zeros(5 * n * 48, dtype=torch.uint8, device=DEV)
+        total = torch.zeros(1, dtype=torch.int32, device=DEV)
+        cf = torch.zeros(n_conns, dtype=torch.int32, device=DEV)
+        fws = torch.empty(fr.workspace_bytes(n), dtype=torch.uint8, device=DEV)
+        f_ms = timed_all(lambda: fr.scan(out, pk, cnt, summ, rec, total, fws, dgrams=dgt, conn_flags=cf), reps)
+        assert int(total[0]) == 5 * n and int((cf != 4).sum()) == 0
+        del rec, fws
+        trk = torch.zeros(3 * n_conns * 528, dtype=torch.uint8, device=DEV)
+        pend = torch.zeros(n_conns, dtype=torch.int32, device=DEV)
+        nx0 = t(np.arange(3 * n_conns, dtype=np.uint64) + np.uint64(100))
+        nx = nx0.clone()
+        max_acks = n_conns + 8
+        frs = torch.zeros(max_acks * ak.FRAME_MAX, dtype=torch.uint8, device=DEV)
+        rq = torch.zeros(max_acks * 48, dtype=torch.uint8, device=DEV)
+        na = torch.zeros(1, dtype=torch.int32, device=DEV)
+        aws = torch.empty(ak.workspace_bytes(n, n_conns), dtype=torch.uint8, device=DEV)
+        b = ak.Build(frs, rq, na, ct, nx, 96)
+        reset_ms = timed(lambda: (trk.zero_(), pend.zero_(), nx.copy_(nx0)), reps)
+        a_ms = [x - reset_ms for x in timed_all(lambda: (trk.zero_(), pend.zero_(), nx.copy_(nx0),
+                                                         ak.track_and_build(pk, cnt, dgt, trk, pend, aws, summary=summ,
+                                                                            conn_flags=cf, build=b)), reps)]
+        # the last timed call against the model, on a sample of connections
+        h_trk = trk.cpu().numpy().view(ak.TRACKER_DTYPE)
+        h_rq, h_fr = rq.cpu().numpy().view(send.REQ_DTYPE), frs.cpu().numpy().reshape(max_acks, ak.FRAME_MAX)
+        assert int(na[0]) == n_conns and int((pend != 0).sum()) == 0
+        assert (h_rq["conn"][:n_conns] == np.arange(n_conns)).all() and (h_rq["conn"][n_conns:] == 0xFFFFFFFF).all()
+        per = pns.reshape(-1, n_conns)
+        for c in sorted(set(int(x) for x in np.random.default_rng(12).choice(n_conns, size=min(k, n_conns), replace=False))):
+            m = am.Tracker()
+            for pn in per[:, c].tolist():
+                m.record(pn)
+            assert am.load_tracker(h_trk[3 * c + 2]).ranges == m.ranges, f"acks sample: tracker of connection {c}"
+            f = am.build_ack_frame(m.ranges)
+            assert h_fr[c, :len(f)].tobytes() == f and h_rq["frame_len"][c] == len(f) and h_rq["pn"][c] == 100 + 3 * c + 2
+        rnd = lambda v: [round(x, 4) for x in v]  # noqa: E731
+        res[name] = {"packets": n, "connections": n_conns, "acks_built": n_conns,
+                     "ranges_per_tracker_mean": round(float(h_trk["n"][2::3].mean()), 2),
+                     "acks_ms_median_min_max": rnd(a_ms), "frames_ms_median_min_max": rnd(f_ms),
+                     "recv_ms_median_min_max": rnd(r_ms), "acks_over_frames": round(a_ms[0] / f_ms[0], 4),
+                     "acks_over_recv": round(a_ms[0] / r_ms[0], 4), "sample_checked": min(k, n_conns), "reps": reps}
+        del summ, trk, aws, pk, dgt
+    return res
+
+
 def main():
+    if len(sys.argv) > 1 and sys.argv[1] == "acks":  # ACK runs only: acks [REPS [BATCH]]
+        assert _lib.load().mq_device_init(0) == 0
+        reps = int(sys.argv[2]) if len(sys.argv) > 2 else 9
+        only = sys.argv[3] if len(sys.argv) > 3 else None
+        print(json.dumps({"device": torch.cuda.get_device_name(0), "acks": bench_acks(reps, only=only)}), flush=True)
+        return
     if len(sys.argv) > 1 and sys.argv[1] == "frames":  # frame index runs only: frames [REPS]
         assert _lib.load().mq_device_init(0) == 0
         reps = int(sys.argv[2]) if len(sys.argv) > 2 else 5
