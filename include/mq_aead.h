@@ -744,6 +744,159 @@ int mq_batch_acks(const mq_recv_pkt* pkts, const uint32_t* n_pkts_dev, uint32_t 
                   const uint32_t* conn_flags, mq_pn_tracker* trackers, uint32_t* ack_pending,
                   uint32_t n_conns, const mq_ack_build* build, void* workspace, void* stream);
 
+/* ---- stream data: per-stream bookkeeping and the payload gather behind the frame index
+ *      (mq_batch_stream_data, mq_batch_stream_read) ------------------------------------------------
+ * What the reference does with a STREAM frame: Frame::Stream in dispatch_frame
+ * (src/connection/recv.rs:620-644) calls StreamMap::get_or_create and mark_recv
+ * (src/transport/stream.rs:227-280, 325-388) and then store_stream_data (src/connection/mod.rs:769-842),
+ * which appends the frame's new bytes to the stream's receive buffer; Frame::ResetStream
+ * (recv.rs:661-669) calls handle_reset (stream.rs:405-424). mq_batch_stream_read is stream_recv
+ * (mod.rs:660-687). The chain is   recv -> frames -> stream_data   on one stream, nothing read back.
+ *
+ * State is one mq_conn_streams per connection, persisting across calls; all-zero means no streams and
+ * no buffers. The reference's default form is meant (no `alloc`, Cargo.toml:9; MAX_STREAMS = 32): both
+ * tables have 32 slots and never grow. The data of buffer slot s of connection c lies at
+ * bufs + ((uint64_t)c * 32 + s) * stream_buf; stream_buf is the reference's const generic STREAM_BUF, a
+ * multiple of 16 from 16 to 2^24.
+ *
+ * Which records are processed. Record k < min(*n_frames_dev, max_frames) is selected when its type is
+ * 0x04 or 0x08..0x0f, frames[k].pkt < min(*n_pkts_dev, max_pkts), the packet's dgram < n_dgrams, that
+ * datagram's conn < n_conns and, for a STREAM record, its data range [offset + payload_offset +
+ * data_pos, .. + data_len) lies inside the arena. Every other record is ignored: no event, no state
+ * change, none of its bytes loaded. Both counts are read on the device. Records of a packet whose
+ * summary is MQ_ERR_FRAME are processed like any others: the reference has dispatched the frames before
+ * the failing one (recv.rs:529-542). The packet level is not checked, as in the reference.
+ *
+ * What happens to a selected record: the result equals the sequential replay of the selected records
+ * in record order, per connection. One mq_stream_evt per selected record is written, in record order.
+ * STREAM (id = v[0], offset = v[1], len = data_len, fin = type & 1):
+ *  1. get_or_create(id, is_client, initial_max_stream_data), result ignored (recv.rs:625-627). The id
+ *     is peer-initiated when (id & 1) == (is_client ? 1 : 0); otherwise nothing is created
+ *     (stream.rs:235-243). An existing entry is found by id; otherwise the first unused map slot is
+ *     taken (NEW_STREAM), or nothing happens if there is none (StreamLimitExhausted). A bidirectional id
+ *     (id & 2 == 0) gets HAS_SEND | HAS_RECV and raises max_bidi_remote to id / 4 + 1; a
+ *     unidirectional id gets HAS_RECV alone and raises max_uni_remote (stream.rs:253-276). The new
+ *     entry has recv_offset 0, recv_max_data = recv_max_data_next = initial_max_stream_data, state
+ *     Recv, no FIN offset (stream.rs:129-137).
+ *  2. If no map entry has this id (recv.rs:630), the event has mark = 0xFF, store = 0 and nothing else
+ *     happens. A caller may have seeded entries for locally opened streams (open_bidi / open_uni,
+ *     stream.rs:186-223); such an entry is found here although its id is not peer-initiated.
+ *  3. mark_recv (stream.rs:325-388), in the reference's order, with its partial effects before an error:
+ *     no HAS_RECV -> InvalidState; state not Recv or SizeKnown -> StreamStateError; end = offset + len;
+ *     with a FIN offset, end > fin -> FinalSizeError and fin && end != fin -> FinalSizeError; with fin,
+ *     fin_offset = end and state SizeKnown; then end > recv_max_data -> FlowControlError (the FIN offset
+ *     and SizeKnown stay set); then recv_offset = max(recv_offset, end); with a FIN offset and
+ *     recv_offset >= fin, state DataRecvd; then the auto-tune on the advanced recv_offset: remaining =
+ *     recv_max_data.saturating_sub(recv_offset), window = recv_max_data_next, and if remaining <
+ *     window / 2 then recv_max_data_next = recv_offset + window. That add is 64-bit wrapping here, where
+ *     the reference would overflow. The result goes into `mark`, and whatever it is, step 4 runs
+ *     (recv.rs:631-639).
+ *  4. store_stream_data (mod.rs:769-842): the first used buffer with this stream_id, else the first
+ *     unused one, which is initialised to zero counters (NEW_BUF), else store = 1. offset > next_offset:
+ *     gap, store = 2, FIN not recorded. offset + len <= next_offset: duplicate, store = 3, fin_received
+ *     set if fin. Otherwise skip = next_offset - offset, copy_len = min(len - skip, stream_buf -
+ *     buf.len), the bytes go to data[buf.len..], buf.len and next_offset advance by copy_len,
+ *     fin_received is set if fin even when the copy was truncated or empty (the reference does so),
+ *     store = 4, and TRUNCATED is set when copy_len < len - skip. FIN_SET says that this record set
+ *     fin_received. A loaded len above stream_buf, or read_offset above len, is clamped on load; used
+ *     and fin_received are read as zero / non-zero and written as 0 / 1.
+ *  5. READABLE (Event::StreamReadable, recv.rs:642) is set whenever step 2 found the stream.
+ * RESET_STREAM (id = v[0], final_size = v[2]): only if a map entry has the id (else mark = 0xFF),
+ * handle_reset: no HAS_RECV -> InvalidState; state not Recv, SizeKnown or DataRecvd -> StreamStateError;
+ * a FIN offset that differs from final_size -> FinalSizeError; otherwise fin_offset = final_size and
+ * state ResetRecvd. RESET (Event::StreamReset) is set when the entry exists. It is in the replay because
+ * it changes what later mark_recv calls on the stream answer.
+ * STOP_SENDING and MAX_STREAM_DATA (recv.rs:650-654, 671-680) touch only the send half, which is not
+ * modelled here: their records are ignored. An event's src, dst, skip and copy_len are 0 unless store
+ * = 4; its reserved bytes are written as 0.
+ *
+ * Known limit: a connection's records are replayed by one group of 32 lanes, so a batch over very few
+ * connections is serial in its bookkeeping; the copy is parallel regardless. */
+#define MQ_STREAM_SLOTS 32
+#define MQ_STREAMS_CLIENT 0x01        /* flags: we are the client, so peer-initiated ids are the odd ones */
+#define MQ_STREAM_WOULD_BLOCK 11      /* mq_stream_read_res.status: Error::WouldBlock (mod.rs:671, 686)   */
+
+typedef struct mq_stream_entry {      /* one Option<StreamState>: the recv half and what get_or_create sets */
+  uint64_t id;
+  uint64_t recv_offset, recv_max_data, recv_max_data_next, fin_offset;
+  uint8_t  flags;                     /* USED 0x01, HAS_RECV 0x02, HAS_SEND 0x04, HAS_FIN 0x08 (fin_offset is Some) */
+  uint8_t  recv_state;                /* 0 Recv, 1 SizeKnown, 2 DataRecvd, 3 ResetRecvd, 4 DataRead, 5 ResetRead */
+  uint8_t  reserved[6];
+} mq_stream_entry;                    /* 48 bytes */
+
+typedef struct mq_stream_buf {        /* one Option<StreamRecvBuf>, without its data */
+  uint64_t stream_id, next_offset;
+  uint32_t len, read_offset;
+  uint8_t  used, fin_received, reserved[6];
+} mq_stream_buf;                      /* 32 bytes */
+
+typedef struct mq_conn_streams {
+  mq_stream_entry map[32];            /* StreamMap::streams */
+  mq_stream_buf   buf[32];            /* QuicStreamIo::recv_bufs */
+  uint64_t max_bidi_remote, max_uni_remote, reserved[2];
+} mq_conn_streams;                    /* 2592 bytes */
+
+typedef struct mq_stream_evt {        /* one per processed STREAM / RESET_STREAM record, in record order */
+  uint32_t frame, conn;               /* record index; connection */
+  uint64_t src;                       /* arena offset of the first byte copied */
+  uint32_t dst;                       /* offset in the stream buffer (= buf.len before the frame) */
+  uint16_t copy_len, skip;
+  uint8_t  map_slot, buf_slot;        /* 0..31, 0xFF = none */
+  uint8_t  mark;                      /* result of mark_recv / handle_reset: 0 Ok, 1 InvalidState, 2 StreamStateError,
+                                         3 FinalSizeError, 4 FlowControlError, 0xFF not run (no stream) */
+  uint8_t  store;                     /* 0 none, 1 no free buffer, 2 gap (dropped), 3 duplicate, 4 copied */
+  uint8_t  flags;                     /* NEW_STREAM 0x01, NEW_BUF 0x02, FIN_SET 0x04, TRUNCATED 0x08,
+                                         READABLE 0x10 (Event::StreamReadable), RESET 0x20 (Event::StreamReset) */
+  uint8_t  type;                      /* the record's type: 0x04, 0x08..0x0f */
+  uint8_t  reserved[2];
+} mq_stream_evt;                      /* 32 bytes */
+
+/* All pointers are device memory. evts has room for max_frames entries; *n_evts (device) receives the
+ * number of selected records and never exceeds max_frames. flags: MQ_STREAMS_CLIENT.
+ * Guarantees: a connection with no selected record is left as it is; one with some is written back
+ * whole (every entry, every buffer header, max_bidi_remote, max_uni_remote); reserved bytes are never
+ * written. Stream data is written to [dst, dst + copy_len) of its buffer and nowhere else; bytes of a
+ * buffer at and beyond len are otherwise left alone (the reference's zero fill of a new buffer is not
+ * observable and is not done). The arena is only read, and only inside selected data ranges. The
+ * output is a function of the inputs alone: the same inputs give the same bytes again.
+ * Host-level returns as for mq_batch_acks: MQ_ERR_INVALID_ARG, checked first with nothing launched, for
+ * max_frames > 2^26, n_conns > 2^30, a stream_buf that is no multiple of 16 from 16 to 2^24, a NULL
+ * workspace or n_evts, a NULL arena, pkts, n_pkts_dev, dgrams, frames, n_frames_dev or evts with
+ * max_frames > 0 and n_conns > 0, a NULL streams or bufs with n_conns > 0, or pkts / dgrams / frames /
+ * streams / evts / workspace not 16-byte aligned; MQ_OK with *n_evts = 0 for max_frames == 0 or n_conns
+ * == 0; MQ_ERR_NO_DEVICE / MQ_ERR_HIP as elsewhere. workspace has
+ * mq_batch_stream_data_workspace_size(max_frames, n_conns) bytes; its contents need not be initialised. */
+size_t mq_batch_stream_data_workspace_size(uint32_t max_frames, uint32_t n_conns);
+int mq_batch_stream_data(const uint8_t* arena, uint64_t arena_len,
+                         const mq_recv_pkt* pkts, const uint32_t* n_pkts_dev, uint32_t max_pkts,
+                         const mq_dgram* dgrams, uint32_t n_dgrams,
+                         const mq_frame* frames, const uint32_t* n_frames_dev, uint32_t max_frames,
+                         mq_conn_streams* streams, uint32_t n_conns,
+                         uint8_t* bufs, uint32_t stream_buf, uint64_t initial_max_stream_data, uint32_t flags,
+                         mq_stream_evt* evts, uint32_t* n_evts, void* workspace, void* stream);
+
+/* Read side: request k is stream_recv(stream_id, &mut out[out_offset .. out_offset + cap])
+ * (mod.rs:660-687) on the first used buffer of connection conn with that id. No such buffer gives
+ * status MQ_STREAM_WOULD_BLOCK. available = len - read_offset (both clamped on load as above). With
+ * available == 0 and fin_received the slot is released (used = 0) and the answer is (0, fin = 1);
+ * without fin_received it is MQ_STREAM_WOULD_BLOCK. Otherwise min(available, cap) bytes are copied and
+ * read_offset advances; fin = fin_received && read_offset >= len, which releases the slot. conn >=
+ * n_conns or an output range outside out_len gives MQ_ERR_INVALID_ARG in the result, with no copy and no
+ * state change. Two requests of one call that name the same buffer: the one with the lowest index is
+ * served, the others get MQ_ERR_DEFERRED and change nothing, so the result is a function of the
+ * inputs. res[k] = { copied, status, fin, slot (0..31, 0xFF = none), 0 }. Output ranges of different
+ * requests must not overlap: that is the caller's contract. Only the buffer headers of served requests
+ * are written (len, read_offset, used); the map is not touched, as in the reference.
+ * Host-level returns: MQ_ERR_INVALID_ARG for n_reqs > 2^26, n_conns > 2^30, a bad stream_buf, a NULL
+ * workspace, a NULL streams, bufs, reqs, out or res with n_reqs > 0, or streams / reqs / workspace not
+ * 16-byte aligned or res not 8-byte aligned; MQ_OK for n_reqs == 0. */
+typedef struct mq_stream_read_req { uint32_t conn, cap; uint64_t stream_id, out_offset, reserved; } mq_stream_read_req; /* 32 */
+typedef struct mq_stream_read_res { uint32_t copied; uint8_t status, fin, slot, reserved; } mq_stream_read_res;        /* 8  */
+size_t mq_batch_stream_read_workspace_size(uint32_t n_reqs, uint32_t n_conns);
+int mq_batch_stream_read(mq_conn_streams* streams, uint32_t n_conns, const uint8_t* bufs, uint32_t stream_buf,
+                         const mq_stream_read_req* reqs, uint32_t n_reqs, uint8_t* out, uint64_t out_len,
+                         mq_stream_read_res* res, void* workspace, void* stream);
+
 /* Batched HeaderProtection::mask: masks[i*5..] = mask(key_table[key_ids[i]].hp, samples[i*16..]).
  * An entry whose key id is out of range or whose row holds no valid suite gets an all-zero mask
  * (the call still returns MQ_OK: validate key ids on the caller's side). */

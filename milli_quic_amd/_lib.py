@@ -28,6 +28,7 @@ MQ_ERR_HIP = 7
 MQ_ERR_TLS = 8
 MQ_ERR_DEFERRED = 9
 MQ_ERR_FRAME = 10
+MQ_STREAM_WOULD_BLOCK = 11  # mq_stream_read_res.status only
 
 MQ_SUITE_AES128GCM = 1
 MQ_SUITE_CHACHA20 = 2
@@ -58,6 +59,9 @@ MQ_CONN_FRAMES_CLOSE, MQ_CONN_FRAMES_ERROR = 0x08, 0x10
 MQ_PN_TRACKER_RANGES = 32
 MQ_ACK_FRAME_MAX = 528
 MQ_ACKS_CLIENT = 0x01
+
+MQ_STREAM_SLOTS = 32
+MQ_STREAMS_CLIENT = 0x01
 
 
 class KeyMaterial(ctypes.Structure):
@@ -184,6 +188,11 @@ SIGNATURES = {
     "mq_batch_frames": (ctypes.c_int, [_vp, _u64, _vp, _vp, _u32, _vp, _u32, _vp, _vp, _u32, _vp, _vp, _u32, _vp, _vp]),
     "mq_batch_acks_workspace_size": (_sz, [_u32, _u32]),
     "mq_batch_acks": (ctypes.c_int, [_vp, _vp, _u32, _vp, _vp, _u32, _vp, _vp, _vp, _u32, ctypes.POINTER(AckBuild), _vp, _vp]),
+    "mq_batch_stream_data_workspace_size": (_sz, [_u32, _u32]),
+    "mq_batch_stream_data": (ctypes.c_int, [_vp, _u64, _vp, _vp, _u32, _vp, _u32, _vp, _vp, _u32, _vp, _u32, _vp, _u32,
+                                            _u64, _u32, _vp, _vp, _vp, _vp]),
+    "mq_batch_stream_read_workspace_size": (_sz, [_u32, _u32]),
+    "mq_batch_stream_read": (ctypes.c_int, [_vp, _u32, _vp, _u32, _vp, _u32, _vp, _u64, _vp, _vp, _vp]),
     "mq_keytable_create": (ctypes.c_int, [ctypes.POINTER(KeyMaterial), _u32, ctypes.POINTER(_vp)]),
     "mq_keytable_update": (ctypes.c_int, [_vp, _u32, ctypes.POINTER(KeyMaterial), _u32]),
     "mq_keytable_rows": (_u32, [_vp]),

@@ -615,6 +615,7 @@ const char* mq_status_str(int status) {
     case MQ_ERR_HIP: return "hip runtime error";
     case MQ_ERR_TLS: return "tls";
     case MQ_ERR_FRAME: return "frame encoding";
+    case MQ_STREAM_WOULD_BLOCK: return "would block";
     default: return "unknown";
   }
 }
@@ -1442,6 +1443,61 @@ int mq_batch_acks(const mq_recv_pkt* pkts, const uint32_t* n_pkts_dev, uint32_t 
   if (!g.ok()) return MQ_ERR_NO_DEVICE;
   return mq_launch_acks(pkts, n_pkts_dev, max_pkts, summary, dgrams, n_dgrams, conn_flags, trackers, ack_pending,
                         n_conns, build, workspace, (hipStream_t)stream) == hipSuccess
+             ? MQ_OK
+             : MQ_ERR_HIP;
+}
+
+// ---- stream bookkeeping and payload gather behind mq_batch_frames (mq_stream_data.hip) ----------
+size_t mq_batch_stream_data_workspace_size(uint32_t max_frames, uint32_t n_conns) {
+  return mq_stream_data_workspace(max_frames, n_conns);
+}
+size_t mq_batch_stream_read_workspace_size(uint32_t n_reqs, uint32_t n_conns) {
+  return mq_stream_read_workspace(n_reqs, n_conns);
+}
+static bool stream_buf_ok(uint32_t stream_buf) {  // STREAM_BUF: a multiple of 16 from 16 to 2^24
+  return stream_buf >= 16 && stream_buf <= (1u << 24) && (stream_buf & 15) == 0;
+}
+
+int mq_batch_stream_data(const uint8_t* arena, uint64_t arena_len, const mq_recv_pkt* pkts, const uint32_t* n_pkts_dev,
+                         uint32_t max_pkts, const mq_dgram* dgrams, uint32_t n_dgrams, const mq_frame* frames,
+                         const uint32_t* n_frames_dev, uint32_t max_frames, mq_conn_streams* streams, uint32_t n_conns,
+                         uint8_t* bufs, uint32_t stream_buf, uint64_t initial_max_stream_data, uint32_t flags,
+                         mq_stream_evt* evts, uint32_t* n_evts, void* workspace, void* stream) {
+  if (max_frames > (1u << 26) || n_conns > (1u << 30) || !stream_buf_ok(stream_buf) || !workspace || !n_evts)
+    return MQ_ERR_INVALID_ARG;
+  if (max_frames && n_conns && (!arena || !pkts || !n_pkts_dev || !dgrams || !frames || !n_frames_dev || !evts))
+    return MQ_ERR_INVALID_ARG;
+  if (n_conns && (!streams || !bufs)) return MQ_ERR_INVALID_ARG;
+  const uintptr_t align = (uintptr_t)pkts | (uintptr_t)dgrams | (uintptr_t)frames | (uintptr_t)streams |
+                          (uintptr_t)evts | (uintptr_t)workspace;
+  if ((align & 15) != 0) return MQ_ERR_INVALID_ARG;
+  const int dev = creation_device();
+  if (dev < 0) return MQ_ERR_NO_DEVICE;
+  DeviceGuard g(dev);
+  if (!g.ok()) return MQ_ERR_NO_DEVICE;
+  hipStream_t s = (hipStream_t)stream;
+  if (max_frames == 0 || n_conns == 0) return hipMemsetAsync(n_evts, 0, 4, s) == hipSuccess ? MQ_OK : MQ_ERR_HIP;
+  return mq_launch_stream_data(arena, arena_len, pkts, n_pkts_dev, max_pkts, dgrams, n_dgrams, frames, n_frames_dev,
+                               max_frames, streams, n_conns, bufs, stream_buf, initial_max_stream_data, flags, evts,
+                               n_evts, workspace, s) == hipSuccess
+             ? MQ_OK
+             : MQ_ERR_HIP;
+}
+
+int mq_batch_stream_read(mq_conn_streams* streams, uint32_t n_conns, const uint8_t* bufs, uint32_t stream_buf,
+                         const mq_stream_read_req* reqs, uint32_t n_reqs, uint8_t* out, uint64_t out_len,
+                         mq_stream_read_res* res, void* workspace, void* stream) {
+  if (n_reqs > (1u << 26) || n_conns > (1u << 30) || !stream_buf_ok(stream_buf) || !workspace) return MQ_ERR_INVALID_ARG;
+  if (n_reqs && (!streams || !bufs || !reqs || !out || !res)) return MQ_ERR_INVALID_ARG;
+  if ((((uintptr_t)streams | (uintptr_t)reqs | (uintptr_t)workspace) & 15) != 0 || ((uintptr_t)res & 7) != 0)
+    return MQ_ERR_INVALID_ARG;
+  const int dev = creation_device();
+  if (dev < 0) return MQ_ERR_NO_DEVICE;
+  DeviceGuard g(dev);
+  if (!g.ok()) return MQ_ERR_NO_DEVICE;
+  if (n_reqs == 0) return MQ_OK;
+  return mq_launch_stream_read(streams, n_conns, bufs, stream_buf, reqs, n_reqs, out, out_len, res, workspace,
+                               (hipStream_t)stream) == hipSuccess
              ? MQ_OK
              : MQ_ERR_HIP;
 }

@@ -152,6 +152,19 @@ hipError_t mq_launch_acks(const mq_recv_pkt* pkts, const uint32_t* n_pkts_dev, u
                           const uint32_t* conn_flags, mq_pn_tracker* trackers, uint32_t* ack_pending, uint32_t n_conns,
                           const mq_ack_build* build, void* workspace, hipStream_t s);
 
+// ---- mq_stream_data.hip -------------------------------------------------------------------------
+size_t mq_stream_data_workspace(uint32_t max_frames, uint32_t n_conns);
+size_t mq_stream_read_workspace(uint32_t n_reqs, uint32_t n_conns);
+hipError_t mq_launch_stream_data(const uint8_t* arena, uint64_t arena_len, const mq_recv_pkt* pkts,
+                                 const uint32_t* n_pkts_dev, uint32_t max_pkts, const mq_dgram* dgrams,
+                                 uint32_t n_dgrams, const mq_frame* frames, const uint32_t* n_frames_dev,
+                                 uint32_t max_frames, mq_conn_streams* streams, uint32_t n_conns, uint8_t* bufs,
+                                 uint32_t stream_buf, uint64_t initial_max_stream_data, uint32_t flags,
+                                 mq_stream_evt* evts, uint32_t* n_evts, void* workspace, hipStream_t s);
+hipError_t mq_launch_stream_read(mq_conn_streams* streams, uint32_t n_conns, const uint8_t* bufs, uint32_t stream_buf,
+                                 const mq_stream_read_req* reqs, uint32_t n_reqs, uint8_t* out, uint64_t out_len,
+                                 mq_stream_read_res* res, void* workspace, hipStream_t s);
+
 #ifdef MQ_STAMPS
 void mq_stamps_set_chacha(uint64_t* p);
 void mq_stamps_set_aes(uint64_t* p);

@@ -25,7 +25,12 @@ stream; median of `reps`). Prints one JSON object; the round's copy lives in pro
            connections in order and over 4096 connections with loss and reordering (gaps of 2..300 with
            p = 0.02, ~40000 with p = 0.001, adjacent packets swapped with p = 0.01); every timed call
            starts from empty trackers; a sample of connections checked against tests/acks_model.py
-Usage: python tools/bench_aux.py [reps] | rekey [reps] | recv reps conns... | route [reps] | frames [reps] | acks [reps [batch]]
+  streamdata  mq_batch_stream_data and mq_batch_stream_read (its own mode only) over 2^20 plaintext packets
+           of 1200 B with one 1150-B STREAM frame each, in order on 32 streams per connection, over 4096 and
+           64 connections: the whole call from empty stream tables, the payload rate (bytes read + written)
+           beside a device-to-device copy of the same bytes, then one read request per buffer; a sample of
+           buffers compared with the arena's bytes
+Usage: python tools/bench_aux.py [reps] | rekey [reps] | recv reps conns... | route [reps] | frames [reps] | acks [reps [batch]] | streamdata [reps [batch]]
 """
 import json
 import os
@@ -613,7 +618,86 @@ def bench_acks(reps, n=1 << 20, L=1200, k=12, only=None):
     return res
 
 
+def bench_streamdata(reps, n=1 << 20, L=1200, k=12, only=None):
+    """mq_batch_stream_data over crafted packet and frame records (the call reads nothing else), then
+    mq_batch_stream_read of every buffer; `only` names the one batch to run (profiler runs)."""
+    from milli_quic_amd import frames as fr, stream_data as sd
+    po, dp, dl = 30, 7, 1150                 # payload offset, the frame's data position and length
+    i = np.arange(n, dtype=np.uint64)
+    arena_h = workload.splitmix_bytes(n * L, seed=5)
+    arena = t(arena_h)
+    res = {}
+    for name, n_conns in (("in_order_4096", 4096), ("in_order_64", 64)):
+        if only is not None and name != only:
+            continue
+        per = n // (n_conns * sd.SLOTS)       # frames per stream
+        stream_buf = (per * dl + 15) // 16 * 16
+        conn = (i % np.uint64(n_conns)).astype(np.uint32)
+        slot = ((i // np.uint64(n_conns)) % np.uint64(sd.SLOTS))
+        nth = i // np.uint64(n_conns * sd.SLOTS)
+        pk = np.zeros(n, dtype=recv.PKT_DTYPE)
+        pk["offset"], pk["len"], pk["dgram"], pk["payload_offset"], pk["level"], pk["pn"] = i * np.uint64(L), L, conn, po, 2, i
+        dg = np.zeros(n_conns, dtype=recv.DGRAM_DTYPE)
+        dg["len"], dg["conn"] = L, np.arange(n_conns)
+        f = np.zeros(n, dtype=fr.FRAME_DTYPE)
+        f["pkt"], f["len"], f["type"], f["level"], f["data_pos"], f["data_len"] = i, dp + dl, 0x0e, 2, dp, dl
+        f["v"][:, 0], f["v"][:, 1] = slot * np.uint64(4) + np.uint64(1), nth * np.uint64(dl)
+        pk_d, dg_d, f_d = t(pk), t(dg), t(f)
+        cnt = torch.tensor([n], dtype=torch.int32, device=DEV)
+        st = torch.zeros(n_conns * sd.CONN_STREAMS_DTYPE.itemsize, dtype=torch.uint8, device=DEV)
+        bufs = torch.zeros(n_conns * sd.SLOTS * stream_buf, dtype=torch.uint8, device=DEV)
+        ev = torch.zeros(n * 32, dtype=torch.uint8, device=DEV)
+        n_ev = torch.zeros(1, dtype=torch.int32, device=DEV)
+        ws = torch.empty(sd.workspace_bytes(n, n_conns), dtype=torch.uint8, device=DEV)
+        reset_ms = timed(lambda: st.zero_(), reps)
+        d_ms = [x - reset_ms for x in timed_all(lambda: (st.zero_(), sd.deliver(
+            arena, pk_d, cnt, dg_d, f_d, cnt, st, bufs, stream_buf, 1 << 40, ev, n_ev, ws, flags=sd.CLIENT)), reps)]
+        h_ev = ev.cpu().numpy().view(sd.EVT_DTYPE)
+        assert int(n_ev[0]) == n and (h_ev["store"] == sd.STORE_COPIED).all() and (h_ev["copy_len"] == dl).all()
+        assert (h_ev["mark"] == 0).all() and (h_ev["buf_slot"] == slot).all()
+        rng = np.random.default_rng(12)
+        for c, s_ in zip(rng.integers(0, n_conns, k), rng.integers(0, sd.SLOTS, k)):
+            at = (int(c) * sd.SLOTS + int(s_)) * stream_buf
+            got = bufs[at:at + per * dl].cpu().numpy()
+            first = int(s_) * n_conns + int(c)
+            rows = arena_h.reshape(n, L)[first::n_conns * sd.SLOTS, po + dp:po + dp + dl]
+            assert got.tobytes() == rows.tobytes(), f"streamdata sample: buffer {s_} of connection {c}"
+        moved = 2.0 * n * dl
+        side = torch.empty(n * dl, dtype=torch.uint8, device=DEV)
+        c_ms = timed_all(lambda: side.copy_(arena[:n * dl]), reps)
+        # read every buffer whole
+        n_reqs = n_conns * sd.SLOTS
+        q = np.zeros(n_reqs, dtype=sd.READ_REQ_DTYPE)
+        j = np.arange(n_reqs, dtype=np.uint64)
+        q["conn"], q["stream_id"] = j // np.uint64(sd.SLOTS), (j % np.uint64(sd.SLOTS)) * np.uint64(4) + np.uint64(1)
+        q["cap"], q["out_offset"] = per * dl, j * np.uint64(per * dl)
+        q_d = t(q)
+        rs = torch.zeros(n_reqs * 8, dtype=torch.uint8, device=DEV)
+        rws = torch.empty(sd.read_workspace_bytes(n_reqs, n_conns), dtype=torch.uint8, device=DEV)
+        st0 = st.clone()
+        copy_ms = timed(lambda: st.copy_(st0), reps)
+        r_ms = [x - copy_ms for x in timed_all(lambda: (st.copy_(st0), sd.read(st, bufs, stream_buf, q_d, side, rs, rws)),
+                                               reps)]
+        h_rs = rs.cpu().numpy().view(sd.READ_RES_DTYPE)
+        assert (h_rs["status"] == 0).all() and (h_rs["copied"] == per * dl).all()
+        rnd = lambda v: [round(x, 4) for x in v]  # noqa: E731
+        res[name] = {"packets": n, "connections": n_conns, "frames_per_stream": per, "stream_buf": stream_buf,
+                     "deliver_ms_median_min_max": rnd(d_ms), "deliver_payload_GBps": round(moved / d_ms[0] / 1e6, 1),
+                     "copy_ms_median_min_max": rnd(c_ms), "copy_GBps": round(moved / c_ms[0] / 1e6, 1),
+                     "read_ms_median_min_max": rnd(r_ms), "read_GBps": round(moved / r_ms[0] / 1e6, 1),
+                     "sample_checked": k, "reps": reps}
+        del bufs, side, ws, ev
+    return res
+
+
 def main():
+    if len(sys.argv) > 1 and sys.argv[1] == "streamdata":  # stream data runs only: streamdata [REPS [BATCH]]
+        assert _lib.load().mq_device_init(0) == 0
+        reps = int(sys.argv[2]) if len(sys.argv) > 2 else 9
+        only = sys.argv[3] if len(sys.argv) > 3 else None
+        print(json.dumps({"device": torch.cuda.get_device_name(0), "streamdata": bench_streamdata(reps, only=only)}),
+              flush=True)
+        return
     if len(sys.argv) > 1 and sys.argv[1] == "acks":  # ACK runs only: acks [REPS [BATCH]]
         assert _lib.load().mq_device_init(0) == 0
         reps = int(sys.argv[2]) if len(sys.argv) > 2 else 9
