@@ -260,12 +260,20 @@ constexpr uint32_t kCcOwnIters = MQ_CC_POOL_ITERS;  // a wave's own iterations b
 constexpr uint32_t kCcPoolSlot = kCcOwnIters * kLanesPerPkt;  // first pooled slot
 
 // Seal also pools every packet's header-protection block (RFC 9001 §5.4.4: ChaCha20 under the HP
-// key, counter and nonce from the 16-B ciphertext sample at pn_offset + 4), as the packet's last
-// pool entry: the sample is ciphertext of keystream block 1, in place after iteration 0, and the
-// pool's second wave-iteration is otherwise idle for waves 2-3 of a 1200-B workgroup (128 keystream
-// blocks + 32 HP blocks = 160 entries < 3 x 64), so the mask costs no extra time and no pass over
-// the batch (r02 ran it as a post-pass kernel: 63 us and 0.23 GB per 2^20 packets). The mask waits
-// in the record until the MAC has read the unprotected header; octet lane 0 then applies it.
+// key, counter and nonce from the 16-B ciphertext sample at pn_offset + 4): the sample is
+// ciphertext of keystream block 1, in place after iteration 0, and roles 2-3 of a 1200-B workgroup
+// have no keystream iteration of the pool to run, so the mask costs no pass over the batch (r02 ran
+// it as a post-pass kernel: 63 us and 0.23 GB per 2^20 packets). The mask waits in the record until
+// the MAC has read the unprotected header; octet lane 0 then applies it.
+// The pool's entries (cc_pool_seal): every packet's pooled keystream blocks first, in packet order,
+// padded to whole wave-iterations, then the HP blocks, two lanes each (chacha20_block_pair: lane l
+// takes HP entry l >> 1, half l & 1), 32 to a wave-iteration. A 1200-B workgroup: 128 keystream
+// blocks on roles 0 and 1, 32 HP blocks on role 2. No iteration holds both kinds, so the keystream
+// iterations run open's form of the block (the content key alone, round one hoisted where the key
+// is wave-uniform, no sample load) and the HP iteration half a block function per lane.
+// -DMQ_CC_HP_INTERLEAVED builds the former pool (cc_pool_run for seal too: each packet's HP block
+// as one lane's whole block behind its keystream entries) for A/B libraries, and the kernels in
+// which the new one costs scratch keep it (the kernels over partition lists: chacha_tile).
 //
 // this packet's 32-B pool record in its wave's scratch: [0] pooled keystream blocks (bits 0-7) | the
 // PN length << 8 (3 bits) when the header-protection block is pooled too | for the workgroup MAC
@@ -284,6 +292,26 @@ struct CcPool {
   bool mac;             // workgroup-uniform: the MAC runs as a workgroup phase (cc_wg_mac)
 };
 
+// What both pools (cc_pool_run, cc_pool_seal) share. Packet q of the workgroup (tile q / 8, octet
+// q % 8) has its record in its wave's scratch behind the image (IMG: bytes of LDS per wave).
+template <uint32_t IMG>
+__device__ __forceinline__ uint32_t* cc_rec(uint8_t* wg, uint32_t q) {
+  return (uint32_t*)(wg + (q >> 3) * IMG + (IMG - kScratchBytes) + 32u * (q & 7));
+}
+// The packet of pool entry e, given on lane q the entries ex[q] of the packets before packet q (an
+// exclusive prefix sum over the KQ packets): the last q with ex[q] <= e, by a binary search whose
+// probes are wave shuffles. A packet without entries is never the answer for an entry that exists.
+template <uint32_t KQ>
+__device__ __forceinline__ uint32_t cc_packet_of(uint32_t ex, uint32_t e) {
+  uint32_t q = 0;
+#pragma unroll
+  for (uint32_t step = KQ / 2; step >= 1; step >>= 1) {
+    const uint32_t v = (uint32_t)__shfl((int)ex, (int)(q + step), kWave);
+    if (v <= e) q += step;
+  }
+  return q;
+}
+
 // IMG: bytes of LDS per wave (kLdsBytes; the long-packet kernels' larger images, chacha_tile);
 // W: waves of the workgroup sharing the pool
 // R1 (open's pool of a single-key kernel: keystream blocks only, no header-protection entries):
@@ -297,9 +325,7 @@ __device__ __forceinline__ void cc_pool_run(const CcPool& pool, uint32_t tid = t
   static_assert(kQ <= kWave, "one packet per lane in the pool scan");
   const int lane = tid & (kWave - 1);
   const uint32_t w = pool.role;
-  auto rec = [&](uint32_t q) -> uint32_t* {
-    return (uint32_t*)(pool.wg + (q >> 3) * IMG + (IMG - kScratchBytes) + 32u * (q & 7));
-  };
+  auto rec = [&](uint32_t q) -> uint32_t* { return cc_rec<IMG>(pool.wg, q); };
   const uint32_t r0l = (uint32_t)lane < kQ ? rec((uint32_t)lane)[0] : 0u;  // lane q: packet q
   const uint32_t nq = (r0l & 0xffu) + ((r0l >> 8 & 7u) ? 1u : 0u);
   const uint32_t incl = wave_incl_scan(nq), excl = incl - nq;
@@ -308,12 +334,7 @@ __device__ __forceinline__ void cc_pool_run(const CcPool& pool, uint32_t tid = t
   sp.base = pool.wg;
   for (uint32_t e0 = kWave * w; e0 < T; e0 += kWave * W) {  // wave-uniform
     const uint32_t e = e0 + (uint32_t)lane;
-    uint32_t q = 0;  // the packet of entry e: the last q with excl[q] <= e
-#pragma unroll
-    for (uint32_t step = kQ / 2; step >= 1; step >>= 1) {
-      const uint32_t v = (uint32_t)__shfl((int)excl, (int)(q + step), kWave);
-      if (v <= e) q += step;
-    }
+    const uint32_t q = cc_packet_of<kQ>(excl, e);
     const uint32_t eq = (uint32_t)__shfl((int)excl, (int)q, kWave);
     const bool act = e < T;
     uint32_t* r = rec(q);
@@ -352,6 +373,79 @@ __device__ __forceinline__ void cc_pool_run(const CcPool& pool, uint32_t tid = t
     }
   }
 }
+
+// Seal's pool with the keystream entries ahead of the header-protection entries (above). One scan
+// over the records' word 0 gives both prefix sums: the pooled keystream blocks (bits 0-7) in the
+// low half, the HP flag (a PN length is recorded) in the high half. Wave-iteration `it` of the pool
+// is a keystream iteration for it < NK = ceil(K / 64) (entries 64 it + lane of the K keystream
+// entries) and an HP iteration behind them (HP entries 32 (it - NK) + lane / 2 of the H); role r
+// takes iterations r, r + W, ... Which kind an iteration is is wave-uniform, and the DPP exchange of
+// the pair block runs with every lane active.
+// R1: the content key is wave-uniform and round one's part of it hoisted (chacha20_round1_uniform)
+template <bool SINGLE, uint32_t IMG = kLdsBytes, uint32_t W = kCcWaves, bool R1 = false, class Sp = LdsSpace>
+__device__ __forceinline__ void cc_pool_seal(const CcPool& pool, uint32_t tid = threadIdx.x) {
+  static_assert(SINGLE || !R1, "round one is hoisted for wave-uniform keys only");
+  constexpr uint32_t kQ = kPktsPerTile * W;  // packets of the workgroup
+  static_assert(kQ <= kWave, "one packet per lane in the pool scan");
+  static_assert(kQ * 0xffu < 0x10000u, "the keystream prefix sums stay in the low half");
+  const int lane = tid & (kWave - 1);
+  auto rec = [&](uint32_t q) -> uint32_t* { return cc_rec<IMG>(pool.wg, q); };
+  const uint32_t r0l = (uint32_t)lane < kQ ? rec((uint32_t)lane)[0] : 0u;  // lane q: packet q
+  const uint32_t nq = (r0l & 0xffu) | ((r0l >> 8 & 7u) ? 0x10000u : 0u);
+  const uint32_t incl = wave_incl_scan(nq), excl = incl - nq;
+  const uint32_t T = lane_u32(incl, kWave - 1);
+  const uint32_t K = T & 0xffffu, H = T >> 16;
+  const uint32_t NK = (K + kWave - 1) / kWave, NI = NK + (H + kWave / 2 - 1) / (kWave / 2);
+  const uint32_t exk = excl & 0xffffu, exh = excl >> 16;
+  Sp sp{};
+  sp.base = pool.wg;
+  for (uint32_t it = __builtin_amdgcn_readfirstlane(pool.role); it < NI; it += W) {  // wave-uniform
+    if (it < NK) {
+      const uint32_t e = kWave * it + (uint32_t)lane;
+      const uint32_t q = cc_packet_of<kQ>(exk, e);
+      const uint32_t eq = (uint32_t)__shfl((int)exk, (int)q, kWave);
+      const bool act = e < K;
+      const uint32_t* r = rec(q);
+      const uint32_t r1 = r[1], pay = r1 & 0x1ffffu, P = r1 >> 17;
+      const uint32_t cb = kCcPoolSlot + (e - eq), o = kKsStride * (cb - 1);
+      const KeyRow* row = SINGLE || !act ? pool.kt : pool.kt + r[3];  // an idle lane's record may be stale
+      uint32_t key[8];
+      load_key8(row->key, key);
+      XorBlock<16, Sp> x;
+      x.load(sp, act ? pay + o : 0u);  // LdsSpaceRaw: in flight during the rounds
+      uint32_t ks[16];
+      if constexpr (R1)
+        chacha20_block(key, cb, r[4], r[5], r[6], chacha20_round1_uniform(key[0], key[1], key[5], row->iv[0]), ks);
+      else
+        chacha20_block(key, cb, r[4], r[5], r[6], ks);
+      if (act) x.apply(sp, pay + o, ks, (int)min(64u, P - o));
+    } else {
+      const uint32_t h = (uint32_t)lane & 1u, g = (kWave / 2) * (it - NK) + ((uint32_t)lane >> 1);
+      const uint32_t q = cc_packet_of<kQ>(exh, g);
+      const bool act = g < H;
+      uint32_t* r = rec(q);
+      const uint32_t pay = r[1] & 0x1ffffu, pn_len = r[0] >> 8 & 7u;
+      const KeyRow* row = SINGLE || !act ? pool.kt : pool.kt + r[3];
+      // this half's columns of the state: two words each of the constants, of both halves of the
+      // HP key and of the sample, the 16 bytes at pn_offset + 4 = payload - pn_len + 4
+      const uint2 kb = *(const uint2*)(row->hp + 2u * h), kc = *(const uint2*)(row->hp + 4u + 2u * h);
+      uint32_t smp[2];
+      load_words<2>(sp, act ? pay + 4u - pn_len + 8u * h : 0u, smp);
+      const uint32_t a[2] = {cc_pair_const(h, 0), cc_pair_const(h, 1)}, b[2] = {kb.x, kb.y}, c[2] = {kc.x, kc.y};
+      uint32_t m0, m1;
+#if MQ_PROF_SKIP & 1  // phase-cost diagnostic build only (tools/phase_cost.py): no rounds
+      m0 = a[0] ^ b[0] ^ c[0] ^ smp[0];
+      m1 = a[1] ^ b[1] ^ c[1] ^ smp[1];
+#else
+      chacha20_block_pair(a, b, c, smp, PairSwapDpp{}, m0, m1);
+#endif
+      if (act && h == 0) {
+        r[2] = m0;
+        r[7] = m1;
+      }
+    }
+  }
+}
 // the pool's space for a tile code running on S (the direct path's tiles pool nothing)
 template <class S> struct PoolSpace { typedef LdsSpace type; };
 template <> struct PoolSpace<LdsSpaceRaw> { typedef LdsSpaceRaw type; };
@@ -376,7 +470,7 @@ __device__ __forceinline__ void cc_wg_mac(uint8_t* wg, uint32_t m, uint32_t tid)
   static_assert(kPktsPerTile * W == 2 * (kWave / G), "two MAC waves of 16 packets");
   const int lane = tid & (kWave - 1), j = lane % G;
   const uint32_t q = (kWave / G) * m + (uint32_t)lane / G;
-  uint32_t* rec = (uint32_t*)(wg + (q >> 3) * IMG + (IMG - kScratchBytes) + 32u * (q & 7));
+  uint32_t* rec = cc_rec<IMG>(wg, q);
   const uint32_t r0 = rec[0], r1 = rec[1];
   const bool act = (r0 & kCcRecMac) != 0;  // else the record's other words may be stale
   const uint32_t aad_len = act ? r0 >> kCcRecAadShift & kCcRecAadMask : 0u;
@@ -518,8 +612,10 @@ struct ChaChaPolicy {
   // WG: the kernel has the workgroup MAC phase (cc_wg_mac), taken when pool.mac says so: a staged
   // tile hands its packets over in their records; a direct-path tile MACs itself, as without the
   // phase, but runs the phase's barrier and its role
-  template <bool SINGLE, uint32_t IMG = kLdsBytes, uint32_t W = kCcWaves, bool R1 = false, bool WG = false, class S,
-            class St>
+  // HP2: the pool runs its header-protection blocks on lane pairs behind the keystream blocks
+  // (cc_pool_seal), else as single-lane entries among them (cc_pool_run)
+  template <bool SINGLE, uint32_t IMG = kLdsBytes, uint32_t W = kCcWaves, bool R1 = false, bool WG = false,
+            bool HP2 = false, class S, class St>
   static __device__ __forceinline__ void seal(const S& sp, typename S::off_t pkt, PktCtx& c, const KeyRow* row, int j,
                                               St& stg, const CcPool& pool) {
     const mq_pkt_desc& d = c.d;
@@ -584,7 +680,8 @@ struct ChaChaPolicy {
       }
     }
     __syncthreads();  // every wave's records
-    cc_pool_run<SINGLE, IMG, W, false, typename PoolSpace<S>::type>(pool);
+    if constexpr (HP2) cc_pool_seal<SINGLE, IMG, W, R1, typename PoolSpace<S>::type>(pool);
+    else cc_pool_run<SINGLE, IMG, W, false, typename PoolSpace<S>::type>(pool);
     __syncthreads();  // every pooled block (and mask) is in place before any MAC reads it
     MQ_STAMP(c.tile, 3);
     uint32_t tag[4] = {0, 0, 0, 0};
@@ -1079,6 +1176,15 @@ __device__ __forceinline__ void chacha_tile(uint32_t tb, uint32_t tid, const Key
   constexpr bool kR1 = SINGLE && SPAN;
   // The workgroup MAC phase (cc_wg_mac) and the rotating roles: the flat kernels over 10-KiB images
   constexpr bool kWg = SPAN && !LIST && IMG == kLdsBytes && W == 4;
+  // Seal's pool with the header-protection blocks on lane pairs (cc_pool_seal): the flat kernels of
+  // every image size, where it changes neither registers nor scratch. Not the kernels over partition
+  // lists, where it costs scratch (bytes per lane: seal lgrid 0 -> 12, seal list 40 -> 72, seal
+  // list1 36 -> 40; lgrid1 one VGPR). The fused protect tile takes it too (kProtectHp2).
+#ifdef MQ_CC_HP_INTERLEAVED
+  constexpr bool kHp2 = false;
+#else
+  constexpr bool kHp2 = !OPEN && !LIST && SPAN;
+#endif
   const bool span_ok = SPAN && (n_rows & kCcNoSpan) == 0;
   const bool wgm = kWg && (n_rows & kCcNoWgMac) == 0;
   n_rows &= ~(kCcNoSpan | kCcNoWgMac);
@@ -1112,7 +1218,8 @@ __device__ __forceinline__ void chacha_tile(uint32_t tb, uint32_t tid, const Key
       if (pool.role >= W - 2) cc_wg_mac<true, IMG, W, SINGLE>(smem, pool.role - (W - 2), tid);
       __syncthreads();
     }
-    cc_pool_run<SINGLE, IMG, W, OPEN && kR1, Sp>(pool, tid);
+    if constexpr (kHp2) cc_pool_seal<SINGLE, IMG, W, kR1, Sp>(pool, tid);
+    else cc_pool_run<SINGLE, IMG, W, OPEN && kR1, Sp>(pool, tid);
     __syncthreads();
     if (kWg && !OPEN && wgm) {
       if (pool.role >= W - 2) cc_wg_mac<false, IMG, W>(smem, pool.role - (W - 2), tid);
@@ -1156,7 +1263,7 @@ __device__ __forceinline__ void chacha_tile(uint32_t tb, uint32_t tid, const Key
     MQ_STAMP(tile_id, 1);
     const uint32_t pkt = pl.slot * 16u + pl.head();
     if (OPEN) ChaChaPolicy::open<kLanesPerPkt, true, SINGLE, IMG, W, kR1, kWg>(sp, pkt, c, row, j, false, stg, pool);
-    else ChaChaPolicy::seal<SINGLE, IMG, W, kR1, kWg>(sp, pkt, c, row, j, stg, pool);
+    else ChaChaPolicy::seal<SINGLE, IMG, W, kR1, kWg, kHp2>(sp, pkt, c, row, j, stg, pool);
     MQ_STAMP(tile_id, 6);
     wave_sync();
     // a packet that failed to open is never stored: such a tile goes back packet by packet
@@ -1167,7 +1274,7 @@ __device__ __forceinline__ void chacha_tile(uint32_t tb, uint32_t tid, const Key
     GlobalSpace sp{arena, arena_len};
     NoStager stg;
     if (OPEN) ChaChaPolicy::open<kLanesPerPkt, true, SINGLE, IMG, W, kR1, kWg>(sp, off, c, row, j, true, stg, pool);
-    else ChaChaPolicy::seal<SINGLE, IMG, W, kR1, kWg>(sp, off, c, row, j, stg, pool);
+    else ChaChaPolicy::seal<SINGLE, IMG, W, kR1, kWg, kHp2>(sp, off, c, row, j, stg, pool);
   }
   tile_status<OPEN>(c, j, status, pn_out);
 }
@@ -1397,6 +1504,13 @@ MQ_CHACHA_NARROW_KERNELS(mq_chacha_seal_narrow1_kernel, mq_chacha_open_narrow1_k
 constexpr uint32_t kProtectBatch = MQ_PROTECT_BATCH;  // image chunks per lane whose loads fly together (5:
                                                       // no spills beside the seal state; 8 or 10 spill)
 
+// Seal's pool with the header-protection blocks on lane pairs (cc_pool_seal), as in the flat seal
+// kernels (chacha_tile): it changes neither kernel's registers (128 / 126 VGPRs) nor adds scratch
+#ifdef MQ_CC_HP_INTERLEAVED
+constexpr bool kProtectHp2 = false;
+#else
+constexpr bool kProtectHp2 = true;
+#endif
 template <bool SINGLE>
 __device__ __forceinline__ void chacha_protect_tile(uint32_t tb, const KeyRow* __restrict__ kt, uint32_t n_rows,
                                                     const mq_conn_send* __restrict__ conns, uint32_t n_conns,
@@ -1416,7 +1530,8 @@ __device__ __forceinline__ void chacha_protect_tile(uint32_t tb, const KeyRow* _
   if (tile0 >= n) {  // a wave past the batch in a live workgroup joins the barriers and the pool
     if (j == 0) pool.rec[0] = 0;
     __syncthreads();
-    cc_pool_run<SINGLE>(pool);
+    if constexpr (kProtectHp2) cc_pool_seal<SINGLE>(pool);
+    else cc_pool_run<SINGLE>(pool);
     __syncthreads();
     return;
   }
@@ -1498,7 +1613,7 @@ __device__ __forceinline__ void chacha_protect_tile(uint32_t tb, const KeyRow* _
 #endif
     LdsSpace sp{wsm};
     NoStager stg;  // complete(): the wave's image stores are done before any lane reads the image
-    ChaChaPolicy::seal<SINGLE>(sp, pl.slot * 16u + pl.head(), c, row, j, stg, pool);
+    ChaChaPolicy::seal<SINGLE, kLdsBytes, kCcWaves, false, false, kProtectHp2>(sp, pl.slot * 16u + pl.head(), c, row, j, stg, pool);
     wave_sync();
     stage_out(wsm, out, lane, c.act, pl);
   } else {
@@ -1506,7 +1621,7 @@ __device__ __forceinline__ void chacha_protect_tile(uint32_t tb, const KeyRow* _
     wave_sync();  // the packets are in HBM before the seal reads them
     GlobalSpace sp{out, out_len};
     NoStager stg;
-    ChaChaPolicy::seal<SINGLE>(sp, c.act ? c.d.offset : 0, c, row, j, stg, pool);
+    ChaChaPolicy::seal<SINGLE, kLdsBytes, kCcWaves, false, false, kProtectHp2>(sp, c.act ? c.d.offset : 0, c, row, j, stg, pool);
   }
   if (c.valid && j == 0) {
     status[c.i] = (uint8_t)c.st;

@@ -19,6 +19,7 @@
 #include "../../include/mq_aead.h"
 #include "mq_poly_sched.h"
 #include "mq_poly26.h"
+#include "mq_chacha_pair.h"
 
 namespace mq {
 
@@ -569,6 +570,13 @@ __device__ __forceinline__ void chacha20_block(const uint32_t (&key)[8], uint32_
   out[8] = x8 + key[4]; out[9] = x9 + key[5]; out[10] = x10 + key[6]; out[11] = x11 + key[7];
   out[12] = x12 + ctr; out[13] = x13 + n0; out[14] = x14 + n1; out[15] = x15 + n2;
 }
+
+// The exchange of the two-lane block function (mq_chacha_pair.h chacha20_block_pair): lanes l and
+// l ^ 1 swap a word. Every lane of the wave must be active. hipcc folds the move into the DPP
+// operand of the add or XOR that consumes it.
+struct PairSwapDpp {
+  __device__ __forceinline__ uint32_t operator()(uint32_t x) const { return quad_swap1(x); }
+};
 
 // Poly1305 arithmetic mod 2^130-5 in radix 2^26 (P26, p26_mul, p26_mul2, p26_finish): mq_poly26.h.
 
