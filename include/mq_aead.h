@@ -897,6 +897,176 @@ int mq_batch_stream_read(mq_conn_streams* streams, uint32_t n_conns, const uint8
                          const mq_stream_read_req* reqs, uint32_t n_reqs, uint8_t* out, uint64_t out_len,
                          mq_stream_read_res* res, void* workspace, void* stream);
 
+/* ---- loss recovery: sent-packet tracking, received ACK frames, RTT, congestion window and timers
+ *      (mq_batch_sent, mq_batch_recovery) -------------------------------------------------------------
+ * What the reference does for every packet it sends (src/connection/transmit.rs:610-619, 743-752:
+ * SentPacketTracker::on_packet_sent, LossDetector::on_ack_eliciting_sent,
+ * CongestionController::on_packet_sent) and for every ACK frame it receives (Frame::Ack in
+ * dispatch_frame, src/connection/recv.rs:563-612: SentPacketTracker::on_ack_received, LossDetector::
+ * on_ack_received / update_rtt / reset_pto_count, CongestionController::on_packet_acked,
+ * detect_lost_packets, remove, on_packet_lost), with Frame::HandshakeDone on a client (recv.rs:692-704)
+ * and Connection::next_timeout (mod.rs:566-568). The three structures are src/transport/recovery.rs,
+ * loss.rs and congestion.rs. The chains are   recv -> frames -> recovery   and   acks -> protect -> sent,
+ * each on one stream with nothing read back.
+ *
+ * State is one mq_conn_recovery per connection, persisting across calls; the struct is plain memory
+ * that the caller may read and write between calls (handle_timeout's on_pto is pto_count += 1,
+ * set_persistent_congestion_threshold a store). mq_recovery_state_init fills a host row as
+ * LossDetector::new and CongestionController::new do. Times are microseconds. An Option of the
+ * reference is a value and a bit of `have`; a connection that a call writes back holds 0 wherever the bit
+ * is clear. The
+ * tracker is the reference's default form (no `alloc`, SENT_PER_SPACE = 128, mod.rs:322): 128 slots
+ * shared by all three levels that never grow. Its capacity rules are silent, as in the reference:
+ * newly_acked holds 32 packets, lost_pns 64, the parsed (gap, range) pairs 16, and a full tracker drops
+ * the send but still counts it in flight. */
+#define MQ_SENT_SLOTS 128                 /* SENT_PER_SPACE default (mod.rs:322); shared by all three levels */
+#define MQ_SENT_USED 0x01                 /* mq_sent_pkt.flags; an all-zero entry is None */
+#define MQ_SENT_ACK_ELICITING 0x02
+#define MQ_SENT_IN_FLIGHT 0x04
+#define MQ_RECOVERY_CONFIRMED 0x01        /* mq_conn_recovery.flags: state == Active (recv.rs:588-589) */
+#define MQ_RECOVERY_CLIENT 0x01           /* mq_batch_recovery flags: HANDSHAKE_DONE records are processed */
+#define MQ_ACKEVT_RTT 0x01                /* mq_ack_evt.flags: update_rtt ran */
+#define MQ_ACKEVT_RANGES_CUT 0x02         /* more than 16 (gap, range) pairs: the rest was dropped */
+#define MQ_ACKEVT_RANGES_BROKE 0x04       /* the walk over the pairs hit `smallest < gap + 2` */
+#define MQ_ACKEVT_LOST_CUT 0x08           /* a 65th loss ended the scan */
+
+typedef struct mq_sent_pkt {        /* SentPacket (recovery.rs:7-14) */
+  uint64_t pn, time_sent;
+  uint16_t size;
+  uint8_t  level, flags;            /* MQ_LEVEL_*, MQ_SENT_* */
+  uint32_t reserved;
+} mq_sent_pkt;                      /* 24 bytes */
+
+typedef struct mq_conn_recovery {
+  /* LossDetector (loss.rs:26-50) */
+  uint64_t largest_acked[3], time_of_last_ack_eliciting[3], loss_time[3];
+  uint64_t smoothed_rtt, rttvar, min_rtt /* UINT64_MAX = none yet */, latest_rtt, max_ack_delay;
+  /* CongestionController (congestion.rs:3-17) */
+  uint64_t cwnd, ssthresh, bytes_in_flight, recovery_start_time, persistent_congestion_threshold,
+           max_datagram_size, minimum_window;
+  uint32_t have;                    /* the Options: bits 0-2 largest_acked[l], 3-5
+                                       time_of_last_ack_eliciting[l], 6-8 loss_time[l], 9 smoothed_rtt,
+                                       10 recovery_start_time */
+  uint32_t pto_count;
+  uint32_t count;                   /* SentPacketTracker::count */
+  uint32_t flags;                   /* MQ_RECOVERY_CONFIRMED: the caller's to set; a HANDSHAKE_DONE record
+                                       under MQ_RECOVERY_CLIENT sets it too */
+  uint64_t reserved;                /* never written */
+  mq_sent_pkt sent[MQ_SENT_SLOTS];  /* entries, in slot order */
+} mq_conn_recovery;                 /* 3264 bytes */
+
+/* Host only, no device needed: cwnd = max(10 * max_datagram_size, 14720), ssthresh = UINT64_MAX, min_rtt
+ * = UINT64_MAX, minimum_window = 2 * max_datagram_size, max_ack_delay and max_datagram_size as given,
+ * everything else 0. MQ_ERR_INVALID_ARG for a NULL row. */
+int mq_recovery_state_init(mq_conn_recovery* host_row, uint64_t max_ack_delay_us, uint64_t max_datagram_size);
+
+/* Send side, behind mq_batch_protect: reqs, status and pkt_len are that call's request, status and
+ * length tables, now[i] the time request i was sent at. Request i is recorded when status[i] == MQ_OK,
+ * reqs[i].conn < n_conns and reqs[i].level < 3; null requests (MQ_CONN_NONE) and failed requests are
+ * skipped. The result equals the replay in request order, per connection, of transmit.rs:610-619: the
+ * packet goes into the lowest free slot as { pn, level, time_sent = now[i], size = (uint16_t)pkt_len[i],
+ * ACK_ELICITING | IN_FLIGHT | USED } and count + 1; with no free slot it is not stored (the `let _ =` at
+ * :610); in either case time_of_last_ack_eliciting[level] = now[i] with its `have` bit, and
+ * bytes_in_flight += pkt_len[i] (the untruncated length). timeouts (optional, n_conns entries) receives
+ * next_timeout of every connection that recorded a request, as described below.
+ * Guarantees: a connection that records nothing is left byte for byte as it is, and its timeout is not
+ * written; one that records something is written back whole (every field but `reserved`, every entry,
+ * unused entries all-zero). The output is a function of the inputs alone.
+ * Host-level returns: MQ_ERR_INVALID_ARG, checked first with nothing launched, for n > 2^26, n_conns >
+ * 2^30, a NULL workspace, a NULL reqs, status, pkt_len or now with n > 0 and n_conns > 0, a NULL rec with
+ * n_conns > 0, reqs / rec / workspace not 16-byte aligned, now / timeouts not 8-byte aligned or pkt_len not 4-byte
+ * aligned; MQ_OK
+ * with nothing launched for n == 0 or n_conns == 0; MQ_ERR_NO_DEVICE / MQ_ERR_HIP as elsewhere. */
+size_t mq_batch_sent_workspace_size(uint32_t n, uint32_t n_conns);
+int mq_batch_sent(const mq_send_req* reqs, const uint8_t* status, const uint32_t* pkt_len, uint32_t n,
+                  const uint64_t* now /* n entries, microseconds */, mq_conn_recovery* rec, uint32_t n_conns,
+                  uint64_t* timeouts /* optional, n_conns */, void* workspace, void* stream);
+
+typedef struct mq_ack_evt {         /* one per processed ACK record, in record order */
+  uint32_t frame, conn;             /* record index, connection */
+  uint16_t n_acked;                 /* entries removed by on_ack_received (all of them) */
+  uint16_t n_acked_cc;              /* of those, handed to on_packet_acked: min(n_acked, 32) */
+  uint16_t n_lost;                  /* lost_pns.len(), <= 64 */
+  uint16_t flags;                   /* MQ_ACKEVT_* */
+  uint32_t lost_first;              /* index of its first mq_lost_pkt (valid even beyond max_lost) */
+  uint32_t reserved;
+  uint64_t largest_newly_acked;     /* pn, when n_acked > 0 (else 0) */
+} mq_ack_evt;                       /* 32 bytes */
+typedef struct mq_lost_pkt { uint64_t pn; uint32_t conn; uint16_t size; uint8_t level, reserved; } mq_lost_pkt; /* 16 bytes */
+
+/* Receive side, behind mq_batch_frames. All pointers are device memory.
+ * Which records are processed. Record k < min(*n_frames_dev, max_frames) is selected when its type is
+ * 0x02 or 0x03 (ACK), or 0x1e (HANDSHAKE_DONE) under MQ_RECOVERY_CLIENT, frames[k].level < 3,
+ * frames[k].pkt < min(*n_pkts_dev, max_pkts), the packet's dgram < n_dgrams, that datagram's conn <
+ * n_conns and, for an ACK, its range bytes [offset + payload_offset + data_pos, .. + data_len) lie inside
+ * the arena. Every other record is ignored and none of its bytes is loaded. Both counts are read on the
+ * device. Records of a packet whose summary is MQ_ERR_FRAME are processed like any others: the
+ * reference has dispatched the frames before the failing one (recv.rs:529-542). level = frames[k].level,
+ * now = dgram_now[pkts[frames[k].pkt].dgram].
+ *
+ * Per connection: first drop_space on both structures for every level whose bit is set in drop_mask[c]
+ * (recovery.rs:162-171, loss.rs:283-288; bytes_in_flight is not reduced, as in the reference); then the
+ * selected records in record order. The result equals this sequential replay.
+ * ACK (largest = v[0], ack_delay = v[1], first_range = v[3], pairs = the range bytes), recv.rs:563-612:
+ *  1. The (gap, range) varint pairs are decoded from the range bytes; a pair that does not fit into
+ *     data_len ends the decoding (mq_batch_frames never emits one). Only the first 16 are kept
+ *     (heapless::Vec<_, 16>, the push result is dropped; RANGES_CUT). The acked ranges (recovery.rs:79-96):
+ *     [largest.saturating_sub(first_range), largest], then for each pair, stop at smallest < gap + 2
+ *     (RANGES_BROKE), else [range_largest.saturating_sub(range), range_largest] with range_largest =
+ *     smallest - gap - 2.
+ *  2. In slot order every used entry of this level whose pn lies in any range is removed, count - 1 each
+ *     (n_acked). The first 32 in slot order are newly_acked (n_acked_cc). largest_newly_acked is the
+ *     removed entry with the largest pn, the lower slot on a tie.
+ *  3. largest_acked[level] = max(existing, largest) (loss.rs:104-113).
+ *  4. If anything was removed: if the time_sent of largest_newly_acked is > 0 and <= now, update_rtt(now -
+ *     time_sent, ack_delay, flags & CONFIRMED) (loss.rs:68-101; RTT); then pto_count = 0.
+ *  5. on_packet_acked(size, time_sent) for each of newly_acked in slot order (congestion.rs:54-72).
+ *  6. detect_lost_packets (loss.rs:117-172): loss_delay = max(max(smoothed_rtt or 333000, latest_rtt) * 9
+ *     / 8, 1000), lost_send_time = now.saturating_sub(loss_delay); in slot order over the used entries of
+ *     the level with pn <= largest_acked[level]: lost when largest_acked >= pn + 3, else when time_sent <=
+ *     lost_send_time, otherwise loss_time = min(loss_time, time_sent + loss_delay). The 65th loss ends the
+ *     scan (LOST_CUT): entries behind it give neither losses nor deadlines. loss_time[level] and its
+ *     `have` bit take the result, None included.
+ *  7. For each lost pn in push order, remove(level, pn) takes the first used entry of the level with that
+ *     pn, then on_packet_lost(size, time_sent, now) (congestion.rs:75-87). One mq_lost_pkt per removed
+ *     entry, in this order.
+ * HANDSHAKE_DONE under MQ_RECOVERY_CLIENT (recv.rs:694-703): flags |= MQ_RECOVERY_CONFIRMED and
+ * drop_space(Handshake) on both structures; an ACK behind it in the same batch sees the confirmed state.
+ *
+ * Outputs: evts (max_frames entries) receives one mq_ack_evt per selected ACK record, in record order,
+ * *n_evts their number; the mq_lost_pkt of all events lie one behind the other in event order, *n_lost is
+ * their total and can EXCEED max_lost, in which case only the first max_lost are written and every
+ * lost_first stays valid. timeouts (optional, n_conns entries): for every connection touched by the call
+ * (a drop bit or a selected record) next_timeout (loss.rs:188-260): the minimum of the loss_times that
+ * are Some and, when some used entry is ack-eliciting and in flight and some
+ * time_of_last_ack_eliciting is Some, the largest of those + pto_duration * 2^min(pto_count, 62)
+ * (wrapping 64-bit arithmetic); UINT64_MAX means None.
+ * Guarantees: a connection with no selected record and no drop bit is left byte for byte as it is and
+ * its timeout is not written; a touched one is written back whole (every field but `reserved`, every
+ * entry, removed and unused entries all-zero). Nothing else is written; the arena is only read, and only
+ * inside selected range bytes. The output is a function of the inputs alone. For times below 2^56 and
+ * windows below 2^48 no intermediate value overflows; beyond that results are unspecified and accesses
+ * stay in bounds. A loaded `count` is never used as an address.
+ * Host-level returns as for mq_batch_acks: MQ_ERR_INVALID_ARG, checked first with nothing launched, for
+ * max_frames > 2^26, n_conns > 2^30, a NULL workspace, n_evts or n_lost, a NULL arena, pkts, n_pkts_dev,
+ * dgrams, dgram_now, frames, n_frames_dev or evts with max_frames > 0 and n_conns > 0, a NULL rec with
+ * n_conns > 0, a NULL lost with max_lost > 0, pkts / dgrams / frames / rec / evts / lost / workspace not
+ * 16-byte aligned or dgram_now / timeouts not 8-byte aligned; max_frames == 0 is MQ_OK (*n_evts =
+ * *n_lost = 0) and the drop mask still applies; MQ_ERR_NO_DEVICE / MQ_ERR_HIP as elsewhere. workspace
+ * has mq_batch_recovery_workspace_size(max_frames, n_conns) bytes; its contents need not be
+ * initialised. */
+size_t mq_batch_recovery_workspace_size(uint32_t max_frames, uint32_t n_conns);
+int mq_batch_recovery(const uint8_t* arena, uint64_t arena_len,
+                      const mq_recv_pkt* pkts, const uint32_t* n_pkts_dev, uint32_t max_pkts,
+                      const mq_dgram* dgrams, uint32_t n_dgrams, const uint64_t* dgram_now /* n_dgrams, us */,
+                      const mq_frame* frames, const uint32_t* n_frames_dev, uint32_t max_frames,
+                      const uint8_t* drop_mask /* optional, n_conns: bits 0-2 = levels to drop first */,
+                      mq_conn_recovery* rec, uint32_t n_conns,
+                      mq_ack_evt* evts, uint32_t* n_evts,
+                      mq_lost_pkt* lost, uint32_t max_lost, uint32_t* n_lost,
+                      uint64_t* timeouts /* optional */, uint32_t flags /* MQ_RECOVERY_CLIENT */,
+                      void* workspace, void* stream);
+
 /* Batched HeaderProtection::mask: masks[i*5..] = mask(key_table[key_ids[i]].hp, samples[i*16..]).
  * An entry whose key id is out of range or whose row holds no valid suite gets an all-zero mask
  * (the call still returns MQ_OK: validate key ids on the caller's side). */

@@ -16,9 +16,10 @@ from .route import Admit, CidTable  # noqa: F401,E402
 from . import frames  # noqa: F401,E402
 from . import acks  # noqa: F401,E402
 from . import stream_data  # noqa: F401,E402
+from . import recovery  # noqa: F401,E402
 
 __all__ = [
-    "Admit", "CidTable", "route", "frames", "acks", "stream_data",
+    "Admit", "CidTable", "route", "frames", "acks", "stream_data", "recovery",
     "Aes128GcmAead", "Aes128GcmProvider", "AesHeaderProtection", "BufferTooSmall", "ChaCha20Poly1305Aead",
     "ChaCha20Provider", "ChaChaHeaderProtection", "CryptoError", "DirectionalKeys", "Error", "HkdfSha256",
     "InvalidArgument", "ProtocolViolation", "nonce",

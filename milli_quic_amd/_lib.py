@@ -63,6 +63,10 @@ MQ_ACKS_CLIENT = 0x01
 MQ_STREAM_SLOTS = 32
 MQ_STREAMS_CLIENT = 0x01
 
+MQ_SENT_SLOTS = 128
+MQ_RECOVERY_CONFIRMED = 0x01
+MQ_RECOVERY_CLIENT = 0x01
+
 
 class KeyMaterial(ctypes.Structure):
     """mq_key_material: what CryptoProvider::aead + ::header_protection consume."""
@@ -193,6 +197,12 @@ SIGNATURES = {
                                             _u64, _u32, _vp, _vp, _vp, _vp]),
     "mq_batch_stream_read_workspace_size": (_sz, [_u32, _u32]),
     "mq_batch_stream_read": (ctypes.c_int, [_vp, _u32, _vp, _u32, _vp, _u32, _vp, _u64, _vp, _vp, _vp]),
+    "mq_recovery_state_init": (ctypes.c_int, [_vp, _u64, _u64]),
+    "mq_batch_sent_workspace_size": (_sz, [_u32, _u32]),
+    "mq_batch_sent": (ctypes.c_int, [_vp, _vp, _vp, _u32, _vp, _vp, _u32, _vp, _vp, _vp]),
+    "mq_batch_recovery_workspace_size": (_sz, [_u32, _u32]),
+    "mq_batch_recovery": (ctypes.c_int, [_vp, _u64, _vp, _vp, _u32, _vp, _u32, _vp, _vp, _vp, _u32, _vp, _vp, _u32,
+                                         _vp, _vp, _vp, _u32, _vp, _vp, _u32, _vp, _vp]),
     "mq_keytable_create": (ctypes.c_int, [ctypes.POINTER(KeyMaterial), _u32, ctypes.POINTER(_vp)]),
     "mq_keytable_update": (ctypes.c_int, [_vp, _u32, ctypes.POINTER(KeyMaterial), _u32]),
     "mq_keytable_rows": (_u32, [_vp]),

@@ -1502,6 +1502,69 @@ int mq_batch_stream_read(mq_conn_streams* streams, uint32_t n_conns, const uint8
              : MQ_ERR_HIP;
 }
 
+// ---- loss recovery behind mq_batch_protect and mq_batch_frames (mq_recovery.hip) -----------------
+size_t mq_batch_sent_workspace_size(uint32_t n, uint32_t n_conns) { return mq_sent_workspace(n, n_conns); }
+size_t mq_batch_recovery_workspace_size(uint32_t max_frames, uint32_t n_conns) {
+  return mq_recovery_workspace(max_frames, n_conns);
+}
+
+// LossDetector::new (loss.rs:53-65) and CongestionController::new (congestion.rs:23-35)
+int mq_recovery_state_init(mq_conn_recovery* row, uint64_t max_ack_delay_us, uint64_t max_datagram_size) {
+  if (!row) return MQ_ERR_INVALID_ARG;
+  memset(row, 0, sizeof(*row));
+  row->min_rtt = UINT64_MAX;
+  row->max_ack_delay = max_ack_delay_us;
+  row->cwnd = 10 * max_datagram_size > 14720 ? 10 * max_datagram_size : 14720;
+  row->ssthresh = UINT64_MAX;
+  row->max_datagram_size = max_datagram_size;
+  row->minimum_window = 2 * max_datagram_size;
+  return MQ_OK;
+}
+
+int mq_batch_sent(const mq_send_req* reqs, const uint8_t* status, const uint32_t* pkt_len, uint32_t n, const uint64_t* now,
+                  mq_conn_recovery* rec, uint32_t n_conns, uint64_t* timeouts, void* workspace, void* stream) {
+  if (n > (1u << 26) || n_conns > (1u << 30) || !workspace) return MQ_ERR_INVALID_ARG;
+  if (n && n_conns && (!reqs || !status || !pkt_len || !now)) return MQ_ERR_INVALID_ARG;
+  if (n_conns && !rec) return MQ_ERR_INVALID_ARG;
+  if ((((uintptr_t)reqs | (uintptr_t)rec | (uintptr_t)workspace) & 15) != 0) return MQ_ERR_INVALID_ARG;
+  if ((((uintptr_t)now | (uintptr_t)timeouts) & 7) != 0 || ((uintptr_t)pkt_len & 3) != 0) return MQ_ERR_INVALID_ARG;
+  const int dev = creation_device();
+  if (dev < 0) return MQ_ERR_NO_DEVICE;
+  DeviceGuard g(dev);
+  if (!g.ok()) return MQ_ERR_NO_DEVICE;
+  if (n == 0 || n_conns == 0) return MQ_OK;
+  const mq::SentArgs a = {reqs, status, pkt_len, n, now, rec, n_conns, timeouts};
+  return mq_launch_sent(a, workspace, (hipStream_t)stream) == hipSuccess ? MQ_OK : MQ_ERR_HIP;
+}
+
+int mq_batch_recovery(const uint8_t* arena, uint64_t arena_len, const mq_recv_pkt* pkts, const uint32_t* n_pkts_dev,
+                      uint32_t max_pkts, const mq_dgram* dgrams, uint32_t n_dgrams, const uint64_t* dgram_now,
+                      const mq_frame* frames, const uint32_t* n_frames_dev, uint32_t max_frames, const uint8_t* drop_mask,
+                      mq_conn_recovery* rec, uint32_t n_conns, mq_ack_evt* evts, uint32_t* n_evts, mq_lost_pkt* lost,
+                      uint32_t max_lost, uint32_t* n_lost, uint64_t* timeouts, uint32_t flags, void* workspace,
+                      void* stream) {
+  if (max_frames > (1u << 26) || n_conns > (1u << 30) || !workspace || !n_evts || !n_lost) return MQ_ERR_INVALID_ARG;
+  if (max_frames && n_conns &&
+      (!arena || !pkts || !n_pkts_dev || !dgrams || !dgram_now || !frames || !n_frames_dev || !evts))
+    return MQ_ERR_INVALID_ARG;
+  if ((n_conns && !rec) || (max_lost && !lost)) return MQ_ERR_INVALID_ARG;
+  const uintptr_t align = (uintptr_t)pkts | (uintptr_t)dgrams | (uintptr_t)frames | (uintptr_t)rec | (uintptr_t)evts |
+                          (uintptr_t)lost | (uintptr_t)workspace;
+  if ((align & 15) != 0 || (((uintptr_t)dgram_now | (uintptr_t)timeouts) & 7) != 0) return MQ_ERR_INVALID_ARG;
+  const int dev = creation_device();
+  if (dev < 0) return MQ_ERR_NO_DEVICE;
+  DeviceGuard g(dev);
+  if (!g.ok()) return MQ_ERR_NO_DEVICE;
+  hipStream_t s = (hipStream_t)stream;
+  if (n_conns == 0) {
+    return hipMemsetAsync(n_evts, 0, 4, s) == hipSuccess && hipMemsetAsync(n_lost, 0, 4, s) == hipSuccess ? MQ_OK
+                                                                                                         : MQ_ERR_HIP;
+  }
+  const mq::RecoveryArgs a = {arena, arena_len, pkts,  n_pkts_dev, max_pkts, dgrams, n_dgrams, dgram_now, frames, n_frames_dev,
+                              max_frames, drop_mask, rec, n_conns, evts, n_evts, lost, max_lost, n_lost, timeouts, flags};
+  return mq_launch_recovery(a, workspace, s) == hipSuccess ? MQ_OK : MQ_ERR_HIP;
+}
+
 // ---- TLS 1.3 records (tcp_tls/record.rs:88-143, connection.rs:546-600) -----------------------
 int mq_record_seal(const mq_aead_ctx* ctx, const uint8_t* nonce, size_t nonce_len, uint8_t* buf,
                    size_t buf_len, size_t payload_len, uint8_t inner_type, size_t* out_len,

@@ -165,6 +165,48 @@ hipError_t mq_launch_stream_read(mq_conn_streams* streams, uint32_t n_conns, con
                                  const mq_stream_read_req* reqs, uint32_t n_reqs, uint8_t* out, uint64_t out_len,
                                  mq_stream_read_res* res, void* workspace, hipStream_t s);
 
+// ---- mq_recovery.hip ----------------------------------------------------------------------------
+namespace mq {
+// mq_batch_sent's and mq_batch_recovery's arguments as they arrive, checked by mq_host.cpp
+struct SentArgs {
+  const mq_send_req* reqs;
+  const uint8_t* status;
+  const uint32_t* pkt_len;
+  uint32_t n;
+  const uint64_t* now;
+  mq_conn_recovery* rec;
+  uint32_t n_conns;
+  uint64_t* timeouts;
+};
+struct RecoveryArgs {
+  const uint8_t* arena;
+  uint64_t arena_len;
+  const mq_recv_pkt* pkts;
+  const uint32_t* n_pkts_dev;
+  uint32_t max_pkts;
+  const mq_dgram* dgrams;
+  uint32_t n_dgrams;
+  const uint64_t* dgram_now;
+  const mq_frame* frames;
+  const uint32_t* n_frames_dev;
+  uint32_t max_frames;
+  const uint8_t* drop_mask;
+  mq_conn_recovery* rec;
+  uint32_t n_conns;
+  mq_ack_evt* evts;
+  uint32_t* n_evts;
+  mq_lost_pkt* lost;
+  uint32_t max_lost;
+  uint32_t* n_lost;
+  uint64_t* timeouts;
+  uint32_t flags;
+};
+}  // namespace mq
+size_t mq_sent_workspace(uint32_t n, uint32_t n_conns);
+size_t mq_recovery_workspace(uint32_t max_frames, uint32_t n_conns);
+hipError_t mq_launch_sent(const mq::SentArgs& a, void* workspace, hipStream_t s);
+hipError_t mq_launch_recovery(const mq::RecoveryArgs& a, void* workspace, hipStream_t s);
+
 #ifdef MQ_STAMPS
 void mq_stamps_set_chacha(uint64_t* p);
 void mq_stamps_set_aes(uint64_t* p);

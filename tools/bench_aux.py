@@ -30,7 +30,10 @@ stream; median of `reps`). Prints one JSON object; the round's copy lives in pro
            64 connections: the whole call from empty stream tables, the payload rate (bytes read + written)
            beside a device-to-device copy of the same bytes, then one read request per buffer; a sample of
            buffers compared with the arena's bytes
-Usage: python tools/bench_aux.py [reps] | rekey [reps] | recv reps conns... | route [reps] | frames [reps] | acks [reps [batch]] | streamdata [reps [batch]]
+  recovery  mq_batch_sent and mq_batch_recovery (its own mode only) over 2^20 packets and 4096 connections: 256
+           sends per connection into fresh rows, then one ACK frame of one packet number per packet, in order;
+           every timed call starts from the same rows; counts, windows, RTT and events checked on the host
+Usage: python tools/bench_aux.py [reps] | rekey [reps] | recv reps conns... | route [reps] | frames [reps] | acks [reps [batch]] | streamdata [reps [batch]] | recovery [reps]
 """
 import json
 import os
@@ -690,7 +693,65 @@ def bench_streamdata(reps, n=1 << 20, L=1200, k=12, only=None):
     return res
 
 
+def bench_recovery(reps, n=1 << 20, n_conns=4096, L=1200):
+    """mq_batch_sent and mq_batch_recovery over crafted request, packet and frame records (the calls read nothing
+    else): packet i belongs to connection i % n_conns and is its (i // n_conns)-th, one ACK frame of one packet
+    number per packet, in order. Each connection sends 256 packets, of which its 128-slot tracker keeps 128 (the rest
+    are the reference's silently dropped sends, still counted in flight), and receives 256 ACKs, 128 of which find
+    their packet."""
+    from milli_quic_amd import frames as fr, recovery as rcv
+    i = np.arange(n, dtype=np.uint64)
+    conn = (i % np.uint64(n_conns)).astype(np.uint32)
+    nth = i // np.uint64(n_conns)
+    per = n // n_conns
+    rq = np.zeros(n, dtype=send.REQ_DTYPE)
+    rq["conn"], rq["level"], rq["pn"] = conn, 2, nth
+    st_d, ln_d = t(np.zeros(n, dtype=np.uint8)), t(np.full(n, L, dtype=np.uint32))
+    rq_d, now_d = t(rq), t(np.uint64(1000) + nth * np.uint64(50))
+    pk = np.zeros(n, dtype=recv.PKT_DTYPE)
+    pk["offset"], pk["len"], pk["dgram"], pk["payload_offset"], pk["level"], pk["pn"] = i * np.uint64(64), 64, i, 30, 2, nth
+    dg = np.zeros(n, dtype=recv.DGRAM_DTYPE)
+    dg["offset"], dg["len"], dg["conn"] = i * np.uint64(64), 64, conn
+    f = np.zeros(n, dtype=fr.FRAME_DTYPE)
+    f["pkt"], f["len"], f["type"], f["level"], f["data_pos"] = i, 5, 0x02, 2, 5
+    f["v"][:, 0], f["v"][:, 1] = nth % np.uint64(rcv.SLOTS), 100
+    pk_d, dg_d, f_d = t(pk), t(dg), t(f)
+    dnow_d = t(np.uint64(40_000) + nth * np.uint64(50))
+    arena = torch.zeros(n * 64, dtype=torch.uint8, device=DEV)
+    cnt = torch.tensor([n], dtype=torch.int32, device=DEV)
+    rows0 = t(rcv.state_rows(n_conns, 25_000, L))
+    rows = rows0.clone()
+    ev = torch.zeros(n * 32, dtype=torch.uint8, device=DEV)
+    lost = torch.zeros(4096 * 16, dtype=torch.uint8, device=DEV)
+    n_ev, n_lo = torch.zeros(1, dtype=torch.int32, device=DEV), torch.zeros(1, dtype=torch.int32, device=DEV)
+    to = torch.zeros(n_conns, dtype=torch.int64, device=DEV)
+    ws_s = torch.empty(rcv.sent_workspace_bytes(n, n_conns), dtype=torch.uint8, device=DEV)
+    ws_r = torch.empty(rcv.workspace_bytes(n, n_conns), dtype=torch.uint8, device=DEV)
+    copy_ms = timed(lambda: rows.copy_(rows0), reps)
+    s_ms = [x - copy_ms for x in timed_all(lambda: (rows.copy_(rows0), rcv.sent(rq_d, st_d, ln_d, now_d, rows, ws_s, timeouts=to)), reps)]
+    sent_rows = rows.clone()
+    h = sent_rows.cpu().numpy().view(rcv.CONN_RECOVERY_DTYPE)
+    assert (h["count"] == rcv.SLOTS).all() and (h["bytes_in_flight"] == per * L).all()
+    assert (h["sent"]["pn"] == np.arange(rcv.SLOTS)).all() and (h["time_of_last_ack_eliciting"][:, 2] == 1000 + (per - 1) * 50).all()
+    r_ms = [x - copy_ms for x in timed_all(lambda: (rows.copy_(sent_rows), rcv.process(
+        arena, pk_d, cnt, dg_d, dnow_d, f_d, cnt, rows, ev, n_ev, lost, n_lo, ws_r, timeouts=to)), reps)]
+    h = rows.cpu().numpy().view(rcv.CONN_RECOVERY_DTYPE)
+    h_ev = ev.cpu().numpy().view(rcv.EVT_DTYPE)
+    assert int(n_ev[0]) == n and int(n_lo[0]) == 0 and (h["count"] == 0).all() and not h["sent"]["flags"].any()
+    assert (h["bytes_in_flight"] == (per - rcv.SLOTS) * L).all() and (h["cwnd"] == max(10 * L, 14720) + rcv.SLOTS * L).all()
+    assert (h_ev["n_acked"] == (nth < rcv.SLOTS)).all() and (h_ev["frame"] == i).all() and (h["smoothed_rtt"] == 39_000).all()
+    rnd = lambda v: [round(x, 4) for x in v]  # noqa: E731
+    return {"packets": n, "connections": n_conns, "sends_per_connection": per, "acks_per_connection": per,
+            "sent_ms_median_min_max": rnd(s_ms), "sent_Mpkts_per_s": round(n / s_ms[0] / 1e3, 1),
+            "recovery_ms_median_min_max": rnd(r_ms), "recovery_Macks_per_s": round(n / r_ms[0] / 1e3, 1), "reps": reps}
+
+
 def main():
+    if len(sys.argv) > 1 and sys.argv[1] == "recovery":  # loss recovery runs only: recovery [REPS]
+        assert _lib.load().mq_device_init(0) == 0
+        reps = int(sys.argv[2]) if len(sys.argv) > 2 else 9
+        print(json.dumps({"device": torch.cuda.get_device_name(0), "recovery": bench_recovery(reps)}), flush=True)
+        return
     if len(sys.argv) > 1 and sys.argv[1] == "streamdata":  # stream data runs only: streamdata [REPS [BATCH]]
         assert _lib.load().mq_device_init(0) == 0
         reps = int(sys.argv[2]) if len(sys.argv) > 2 else 9
