@@ -21,10 +21,9 @@
 //            prefix sum over the lanes places it, each lane stores its own bytes; lane 0 writes the
 //            request. The same grid writes the null requests behind the last ACK.
 // Every output is a function of the inputs: no atomics.
-#include <hipcub/hipcub.hpp>
+#include "mq_replay.h"  // first: mq_acks.h needs the HIP runtime's qualifiers
 
 #include "mq_acks.h"
-#include "mq_device.h"
 #include "mq_launch.h"
 
 namespace mq {
@@ -35,8 +34,7 @@ constexpr uint32_t kAckGroupsPerBlock = kAckBlock / kAckGroup;
 static_assert(kAckGroup == kAckRanges, "one lane per range");
 static_assert(sizeof(mq_pn_tracker) == 528 && sizeof(mq_send_req) == 48 && sizeof(mq_recv_pkt) == 32, "ABI");
 
-struct AcksWs {
-  uint32_t *keys_in, *keys, *idx_in, *idx;  // max_pkts each
+struct AcksWs : SortWs {                    // max_pkts each
   uint32_t *flags, *pos;                    // max_pkts + 1: run starts, their exclusive scan
   uint32_t* run_key;                        // max_pkts
   uint64_t *run_first, *run_last;           // max_pkts
@@ -45,16 +43,7 @@ struct AcksWs {
   size_t cub_bytes;
 };
 
-// ---- the group's 32 lanes --------------------------------------------------------------------------
-__device__ __forceinline__ uint32_t group_ballot(bool p, uint32_t group_first) {
-  return (uint32_t)(__builtin_amdgcn_ballot_w64(p) >> group_first);
-}
-// the value of the group's lane `src` (0..31; any value is taken modulo 32)
-__device__ __forceinline__ uint64_t group_get(uint64_t v, uint32_t src) {
-  const uint32_t lo = (uint32_t)__shfl((int)(uint32_t)v, (int)(src & 31u), (int)kAckGroup);
-  const uint32_t hi = (uint32_t)__shfl((int)(uint32_t)(v >> 32), (int)(src & 31u), (int)kAckGroup);
-  return lo | (uint64_t)hi << 32;
-}
+using AckLanes = LaneGroup<kAckGroup>;
 
 // One tracker over the group: lane r holds range r; n is the same in all lanes.
 struct LaneTracker {
@@ -65,7 +54,7 @@ struct LaneTracker {
   __device__ __forceinline__ bool valid() const { return lane < n; }
   // lanes >= from take the range of lane + k
   __device__ __forceinline__ void close_up(uint32_t from, uint32_t k) {
-    const uint64_t ns = group_get(s, lane + k), ne = group_get(e, lane + k);
+    const uint64_t ns = AckLanes::get64(s, lane + k), ne = AckLanes::get64(e, lane + k);
     if (lane >= from) s = ns, e = ne;
     n -= k;
   }
@@ -73,16 +62,16 @@ struct LaneTracker {
   // inside the group, and a cross-lane step reads lanes of its own group only: the wave's other group
   // may be in another branch
   __device__ __forceinline__ void record_run(bool on, uint64_t first, uint64_t last) {
-    const uint32_t in = group_ballot(on && valid() && ack_contains(s, e, first), group_first);
-    const uint32_t up = group_ballot(on && valid() && ack_extends_up(e, first), group_first);
-    const uint32_t down = group_ballot(on && valid() && ack_extends_down(s, first), group_first);
+    const uint32_t in = AckLanes::ballot(on && valid() && ack_contains(s, e, first), group_first);
+    const uint32_t up = AckLanes::ballot(on && valid() && ack_extends_up(e, first), group_first);
+    const uint32_t down = AckLanes::ballot(on && valid() && ack_extends_down(s, first), group_first);
     uint32_t at;
     if (in) {
       at = (uint32_t)__builtin_ctz(in);
     } else if (up && down) {  // first bridges range `at` and the one above it
       at = (uint32_t)__builtin_ctz(up);
       const uint32_t ri = (uint32_t)__builtin_ctz(down);
-      const uint64_t re = group_get(e, ri);
+      const uint64_t re = AckLanes::get64(e, ri);
       if (lane == at) e = re;
       close_up(ri, 1);
     } else if (up) {
@@ -93,9 +82,9 @@ struct LaneTracker {
       if (lane == at) s = first;
     } else {  // a new stand-alone range; a full tracker loses its lowest range first
       if (on && n == kAckRanges) close_up(0, 1);
-      const uint32_t above = group_ballot(on && valid() && s > first, group_first);
+      const uint32_t above = AckLanes::ballot(on && valid() && s > first, group_first);
       at = above ? (uint32_t)__builtin_ctz(above) : n;
-      const uint64_t ps = group_get(s, lane - 1), pe = group_get(e, lane - 1);
+      const uint64_t ps = AckLanes::get64(s, lane - 1), pe = AckLanes::get64(e, lane - 1);
       if (on) {
         if (lane > at) s = ps, e = pe;
         if (lane == at) s = e = first;
@@ -103,11 +92,11 @@ struct LaneTracker {
       }
     }
     // the rest of the run: range `at` rises to `last` and takes in the ranges it now reaches
-    uint64_t end = group_get(e, at);
+    uint64_t end = AckLanes::get64(e, at);
     if (last > end) end = last;
-    const uint32_t reach = group_ballot(on && valid() && lane > at && s <= end + 1, group_first);
+    const uint32_t reach = AckLanes::ballot(on && valid() && lane > at && s <= end + 1, group_first);
     const uint32_t k = (uint32_t)__builtin_popcount(reach);
-    const uint64_t top = group_get(e, at + k);  // the last range taken in holds the largest end
+    const uint64_t top = AckLanes::get64(e, at + k);  // the last range taken in holds the largest end
     if (k && top > end) end = top;
     if (on && lane == at) e = end;
     if (k) close_up(at + 1, k);
@@ -119,23 +108,20 @@ struct LaneTracker {
 using namespace mq;
 
 // key: which tracker a packet is recorded in
-__global__ __launch_bounds__(kAckBlock) void mq_acks_key_kernel(
-    const mq_recv_pkt* __restrict__ pkts, const uint32_t* __restrict__ n_pkts_dev, uint32_t max_pkts,
-    const mq_pkt_frames* __restrict__ summary, const mq_dgram* __restrict__ dgrams, uint32_t n_dgrams, uint32_t n_conns,
-    AcksWs ws) {
+__global__ __launch_bounds__(kAckBlock) void mq_acks_key_kernel(AcksArgs a, AcksWs ws) {
   const uint32_t i = blockIdx.x * kAckBlock + threadIdx.x;
-  if (i >= max_pkts) return;
-  const uint32_t n_dev = *n_pkts_dev;
-  const uint32_t n_pkts = n_dev < max_pkts ? n_dev : max_pkts;
-  uint32_t key = 3u * n_conns;
+  if (i >= a.max_pkts) return;
+  const uint32_t n_dev = *a.n_pkts_dev;
+  const uint32_t n_pkts = n_dev < a.max_pkts ? n_dev : a.max_pkts;
+  uint32_t key = 3u * a.n_conns;
   if (i < n_pkts) {
-    const uint4 b = reinterpret_cast<const uint4*>(pkts + i)[1];  // len, dgram, payload_offset + level + status, ..
+    const uint4 b = reinterpret_cast<const uint4*>(a.pkts + i)[1];  // len, dgram, payload_offset + level + status, ..
     const uint32_t level = (b.z >> 16) & 0xFFu, status = b.z >> 24;
-    bool ok = status == MQ_OK && level < 3 && b.y < n_dgrams;
-    if (ok && summary) ok = summary[i].status == MQ_OK;
+    bool ok = status == MQ_OK && level < 3 && b.y < a.n_dgrams;
+    if (ok && a.summary) ok = a.summary[i].status == MQ_OK;
     if (ok) {
-      const uint32_t c = dgrams[b.y].conn;
-      if (c < n_conns) key = 3u * c + level;
+      const uint32_t c = a.dgrams[b.y].conn;
+      if (c < a.n_conns) key = 3u * c + level;
     }
   }
   ws.keys_in[i] = key;
@@ -178,20 +164,14 @@ __global__ __launch_bounds__(kAckBlock) void mq_acks_replay_kernel(mq_pn_tracker
                                                                    uint32_t n_conns, AcksWs ws) {
   const uint32_t t = blockIdx.x * kAckGroupsPerBlock + threadIdx.x / kAckGroup;
   LaneTracker tr;
-  tr.lane = threadIdx.x & (kAckGroup - 1);
-  tr.group_first = threadIdx.x & (kWave - 1) & ~(kAckGroup - 1);
+  tr.lane = AckLanes::lane();
+  tr.group_first = AckLanes::first();
   tr.s = tr.e = 0, tr.n = 0;
   const uint32_t n_runs = ws.pos[max_pkts];  // <= max_pkts
-  uint32_t r = n_runs;
-  if (t < 3u * n_conns) {  // the tracker's first run: lower bound of t in the ascending run keys
-    uint32_t lo = 0, hi = n_runs;
-    while (lo < hi) {
-      const uint32_t mid = lo + (hi - lo) / 2;
-      if (ws.run_key[mid] < t) lo = mid + 1;
-      else hi = mid;
-    }
-    r = lo;
-  }
+  // the tracker's first run. The walk below compares every run's key, which costs no more than the
+  // search for the run's end would, so that end goes unused
+  uint32_t r = n_runs, r_end;
+  if (t < 3u * n_conns) key_run(ws.run_key, n_runs, t, r, r_end);
   bool on = r < n_runs && ws.run_key[r] == t;
   const bool touched = on;
   if (touched) {
@@ -273,7 +253,7 @@ __global__ __launch_bounds__(kAckBlock) void mq_acks_build_kernel(const mq_pn_tr
     // lane r: range r and the start of the range above it
     uint64_t s = 0, e = 0;
     if (on && lane < n) s = trackers[t].range[lane][0], e = trackers[t].range[lane][1];
-    const uint64_t next_start = group_get(s, lane + 1);
+    const uint64_t next_start = AckLanes::get64(s, lane + 1);
     const uint32_t w = on && lane + 1 < n ? ack_pair_bytes(s, e, next_start) : 0u;
     // the pairs go out from range n - 2 down: lane r's pair lies behind those of the lanes above it
     uint32_t incl = w;
@@ -284,7 +264,7 @@ __global__ __launch_bounds__(kAckBlock) void mq_acks_build_kernel(const mq_pn_tr
     }
     const uint32_t all = (uint32_t)__shfl((int)incl, (int)(kAckGroup - 1), (int)kAckGroup);
     if (on) {
-      const uint64_t top_s = group_get(s, n - 1), top_e = group_get(e, n - 1);
+      const uint64_t top_s = AckLanes::get64(s, n - 1), top_e = AckLanes::get64(e, n - 1);
       const uint32_t head = ack_head_bytes(n, top_s, top_e);
       AckSlot put = {b.ack_frames + (size_t)kAckFrameMax * k};
       if (lane + 1 == n) ack_head_put(put, n, s, e);
@@ -309,87 +289,57 @@ __global__ __launch_bounds__(kAckBlock) void mq_acks_build_kernel(const mq_pn_tr
 
 // ---- host side -----------------------------------------------------------------------------------------
 namespace {
-size_t acks_al256(size_t b) { return (b + 255) & ~(size_t)255; }
-uint32_t acks_key_bits(uint32_t n_conns) {  // the keys are 0 .. 3 n_conns
-  uint32_t bits = 1;
-  while (bits < 32 && (3ull * n_conns) >> bits) ++bits;
-  return bits;
-}
-size_t acks_cub_bytes(uint32_t max_pkts, uint32_t n_conns) {
-  size_t a = 0, b = 0, c = 0;
-  (void)hipcub::DeviceRadixSort::SortPairs(nullptr, a, (const uint32_t*)nullptr, (uint32_t*)nullptr,
-                                           (const uint32_t*)nullptr, (uint32_t*)nullptr, (int)max_pkts, 0,
-                                           (int)acks_key_bits(n_conns));
-  (void)hipcub::DeviceScan::ExclusiveSum(nullptr, b, (const uint32_t*)nullptr, (uint32_t*)nullptr, (int)max_pkts + 1);
-  (void)hipcub::DeviceScan::ExclusiveSum(nullptr, c, (const uint32_t*)nullptr, (uint32_t*)nullptr, (int)n_conns + 1);
-  return a > b ? (a > c ? a : c) : (b > c ? b : c);
-}
-size_t acks_layout(uint32_t n, uint32_t n_conns, void* base, AcksWs* w) {
-  size_t off = 0;
-  auto take = [&](size_t bytes) {
-    const size_t at = off;
-    off += acks_al256(bytes);
-    return base ? (uint8_t*)base + at : nullptr;
-  };
-  uint8_t* p[11];
-  for (int q = 0; q < 4; ++q) p[q] = take(4 * (size_t)n);
-  p[4] = take(4 * ((size_t)n + 1));
-  p[5] = take(4 * ((size_t)n + 1));
-  p[6] = take(4 * (size_t)n);
-  p[7] = take(8 * (size_t)n);
-  p[8] = take(8 * (size_t)n);
-  p[9] = take(4 * ((size_t)n_conns + 1));
-  p[10] = take(4 * ((size_t)n_conns + 1));
-  const size_t cb = acks_cub_bytes(n, n_conns);
-  uint8_t* cub = take(cb);
-  if (w) {
-    w->keys_in = (uint32_t*)p[0], w->keys = (uint32_t*)p[1], w->idx_in = (uint32_t*)p[2], w->idx = (uint32_t*)p[3];
-    w->flags = (uint32_t*)p[4], w->pos = (uint32_t*)p[5], w->run_key = (uint32_t*)p[6];
-    w->run_first = (uint64_t*)p[7], w->run_last = (uint64_t*)p[8];
-    w->due = (uint32_t*)p[9], w->base = (uint32_t*)p[10];
-    w->cub = cub, w->cub_bytes = cb;
-  }
-  return off;
+size_t acks_layout(uint32_t n, uint32_t n_conns, void* base, AcksWs& w) {
+  Carve c(base);
+  w.keys_in = c.take<uint32_t>(n);
+  w.keys = c.take<uint32_t>(n);
+  w.idx_in = c.take<uint32_t>(n);
+  w.idx = c.take<uint32_t>(n);
+  w.flags = c.take<uint32_t>((size_t)n + 1);
+  w.pos = c.take<uint32_t>((size_t)n + 1);
+  w.run_key = c.take<uint32_t>(n);
+  w.run_first = c.take<uint64_t>(n);
+  w.run_last = c.take<uint64_t>(n);
+  w.due = c.take<uint32_t>((size_t)n_conns + 1);
+  w.base = c.take<uint32_t>((size_t)n_conns + 1);
+  w.cub_bytes = cub_temp_bytes<true>(n, key_bits(3ull * n_conns), {n + 1, n_conns + 1});
+  w.cub = c.take<uint8_t>(w.cub_bytes);
+  return c.bytes();  // no slack behind the last piece, unlike sent, recovery and stream read
 }
 }  // namespace
 
-size_t mq_acks_workspace(uint32_t max_pkts, uint32_t n_conns) { return acks_layout(max_pkts, n_conns, nullptr, nullptr); }
-
-hipError_t mq_launch_acks(const mq_recv_pkt* pkts, const uint32_t* n_pkts_dev, uint32_t max_pkts,
-                          const mq_pkt_frames* summary, const mq_dgram* dgrams, uint32_t n_dgrams,
-                          const uint32_t* conn_flags, mq_pn_tracker* trackers, uint32_t* ack_pending, uint32_t n_conns,
-                          const mq_ack_build* build, void* workspace, hipStream_t s) {
+size_t mq_acks_workspace(uint32_t max_pkts, uint32_t n_conns) {
   AcksWs w = {};
-  acks_layout(max_pkts, n_conns, workspace, &w);
+  return acks_layout(max_pkts, n_conns, nullptr, w);
+}
+
+hipError_t mq_launch_acks(const AcksArgs& a, void* workspace, hipStream_t s) {
+  AcksWs w = {};
+  acks_layout(a.max_pkts, a.n_conns, workspace, w);
   hipError_t e;
   const dim3 block(kAckBlock);
   auto blocks = [](uint64_t threads) { return dim3((uint32_t)((threads + kAckBlock - 1) / kAckBlock)); };
-  if (max_pkts && n_conns) {
-    hipLaunchKernelGGL(mq_acks_key_kernel, blocks(max_pkts), block, 0, s, pkts, n_pkts_dev, max_pkts, summary, dgrams,
-                       n_dgrams, n_conns, w);
+  if (a.max_pkts && a.n_conns) {
+    hipLaunchKernelGGL(mq_acks_key_kernel, blocks(a.max_pkts), block, 0, s, a, w);
     if ((e = hipGetLastError()) != hipSuccess) return e;
-    size_t cb = w.cub_bytes;
-    if ((e = hipcub::DeviceRadixSort::SortPairs(w.cub, cb, w.keys_in, w.keys, w.idx_in, w.idx, (int)max_pkts, 0,
-                                                (int)acks_key_bits(n_conns), s)) != hipSuccess)
-      return e;
-    hipLaunchKernelGGL(mq_acks_flag_kernel, blocks((uint64_t)max_pkts + 1), block, 0, s, pkts, max_pkts, n_conns, w);
+    if ((e = sort_by_key(w, a.max_pkts, key_bits(3ull * a.n_conns), s)) != hipSuccess) return e;
+    hipLaunchKernelGGL(mq_acks_flag_kernel, blocks((uint64_t)a.max_pkts + 1), block, 0, s, a.pkts, a.max_pkts, a.n_conns, w);
     if ((e = hipGetLastError()) != hipSuccess) return e;
-    cb = w.cub_bytes;
-    if ((e = hipcub::DeviceScan::ExclusiveSum(w.cub, cb, w.flags, w.pos, (int)max_pkts + 1, s)) != hipSuccess) return e;
-    hipLaunchKernelGGL(mq_acks_runs_kernel, blocks(max_pkts), block, 0, s, pkts, max_pkts, n_conns, w);
+    if ((e = exclusive_sum(w, w.flags, w.pos, a.max_pkts + 1, s)) != hipSuccess) return e;
+    hipLaunchKernelGGL(mq_acks_runs_kernel, blocks(a.max_pkts), block, 0, s, a.pkts, a.max_pkts, a.n_conns, w);
     if ((e = hipGetLastError()) != hipSuccess) return e;
-    hipLaunchKernelGGL(mq_acks_replay_kernel, blocks(3ull * n_conns * kAckGroup), block, 0, s, trackers, max_pkts,
-                       n_conns, w);
+    hipLaunchKernelGGL(mq_acks_replay_kernel, blocks(3ull * a.n_conns * kAckGroup), block, 0, s, a.trackers, a.max_pkts,
+                       a.n_conns, w);
     if ((e = hipGetLastError()) != hipSuccess) return e;
   }
-  hipLaunchKernelGGL(mq_acks_due_kernel, blocks((uint64_t)n_conns + 1), block, 0, s, conn_flags, trackers, ack_pending,
-                     n_conns, build != nullptr, w);
+  hipLaunchKernelGGL(mq_acks_due_kernel, blocks((uint64_t)a.n_conns + 1), block, 0, s, a.conn_flags, a.trackers,
+                     a.ack_pending, a.n_conns, a.build != nullptr, w);
   if ((e = hipGetLastError()) != hipSuccess) return e;
-  if (!build) return hipSuccess;
-  size_t cb = w.cub_bytes;
-  if ((e = hipcub::DeviceScan::ExclusiveSum(w.cub, cb, w.due, w.base, (int)n_conns + 1, s)) != hipSuccess) return e;
-  const uint64_t threads = (uint64_t)n_conns * kAckGroup > build->max_acks ? (uint64_t)n_conns * kAckGroup : build->max_acks;
-  hipLaunchKernelGGL(mq_acks_build_kernel, blocks(threads ? threads : 1), block, 0, s, trackers, ack_pending, n_conns,
-                     *build, w);
+  if (!a.build) return hipSuccess;
+  if ((e = exclusive_sum(w, w.due, w.base, a.n_conns + 1, s)) != hipSuccess) return e;
+  const uint64_t threads =
+      (uint64_t)a.n_conns * kAckGroup > a.build->max_acks ? (uint64_t)a.n_conns * kAckGroup : a.build->max_acks;
+  hipLaunchKernelGGL(mq_acks_build_kernel, blocks(threads ? threads : 1), block, 0, s, a.trackers, a.ack_pending,
+                     a.n_conns, *a.build, w);
   return hipGetLastError();
 }

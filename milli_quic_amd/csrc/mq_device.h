@@ -358,6 +358,10 @@ __device__ __forceinline__ uint32_t oct_xor(uint32_t x) {
 // __syncthreads() it is safe in multi-wave workgroups whose waves take different paths.
 // this wave's index in its workgroup (scalar)
 __device__ __forceinline__ uint32_t wave_id() { return __builtin_amdgcn_readfirstlane(threadIdx.x >> 6); }
+// set bits of a wave mask below this lane
+__device__ __forceinline__ uint32_t lanes_below(uint64_t m) {
+  return __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+}
 
 __device__ __forceinline__ void wave_sync() {
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");

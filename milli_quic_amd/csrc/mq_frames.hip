@@ -21,9 +21,8 @@
 //   emit     writes summary.first; a packet with records is walked again up to its last record, and the
 //            records whose index is below max_frames are stored, three 16-B stores spread over the lanes.
 // Every output is a function of the inputs: no atomics but the OR into conn_flags.
-#include <hipcub/hipcub.hpp>
+#include "mq_replay.h"  // first: mq_frames.h needs the HIP runtime's qualifiers
 
-#include "mq_device.h"
 #include "mq_frames.h"
 #include "mq_launch.h"
 
@@ -149,34 +148,30 @@ using namespace mq;
 
 // Emit = false: the count pass. Emit = true: the emit pass (walks up to the packet's last record).
 template <bool Emit>
-__global__ __launch_bounds__(kFrameBlock) void mq_frames_kernel(
-    const uint8_t* __restrict__ arena, uint64_t arena_len, const mq_recv_pkt* __restrict__ pkts,
-    const uint32_t* __restrict__ n_pkts_dev, uint32_t max_pkts, const mq_dgram* __restrict__ dgrams, uint32_t n_dgrams,
-    mq_pkt_frames* __restrict__ summary, mq_frame* __restrict__ frames, uint32_t max_frames,
-    uint32_t* __restrict__ n_frames, uint32_t* __restrict__ conn_flags, uint32_t n_conns, FramesWs ws) {
+__global__ __launch_bounds__(kFrameBlock) void mq_frames_kernel(FramesArgs a, FramesWs ws) {
   __shared__ uint4 win[kFrameBlock];
   const uint32_t lane = threadIdx.x & (kFrameLanes - 1);
   const uint32_t group_first = threadIdx.x & (kWave - 1) & ~(kFrameLanes - 1);
   const uint32_t i = blockIdx.x * kFramePktsPerBlock + threadIdx.x / kFrameLanes;
-  if (i >= max_pkts) return;
-  const uint32_t n_dev = *n_pkts_dev;
-  const uint32_t n_pkts = n_dev < max_pkts ? n_dev : max_pkts;
+  if (i >= a.max_pkts) return;
+  const uint32_t n_dev = *a.n_pkts_dev;
+  const uint32_t n_pkts = n_dev < a.max_pkts ? n_dev : a.max_pkts;
   uint32_t want = 0, first = 0;
   if (Emit) {
-    if (i == 0 && lane == 0) *n_frames = ws.first[max_pkts];
+    if (i == 0 && lane == 0) *a.n_frames = ws.first[a.max_pkts];
     if (i >= n_pkts) return;
     first = ws.first[i];
     want = ws.counts[i];
-    if (lane == 0) summary[i].first = first;
+    if (lane == 0) a.summary[i].first = first;
     if (want == 0) return;
   } else if (i >= n_pkts) {
     if (lane == 0) {
       ws.counts[i] = 0;
-      if (i + 1 == max_pkts) ws.counts[max_pkts] = 0;
+      if (i + 1 == a.max_pkts) ws.counts[a.max_pkts] = 0;
     }
     return;
   }
-  const PktRange r = pkt_range(arena, arena_len, pkts + i);
+  const PktRange r = pkt_range(a.arena, a.arena_len, a.pkts + i);
   uint32_t status = r.status, recs = 0, pads = 0, err_pos = 0, flags = 0, close = 0;
   if (status == MQ_OK && r.len) {
     FrameWindow w;
@@ -207,8 +202,8 @@ __global__ __launch_bounds__(kFrameBlock) void mq_frames_kernel(
       if (frame_is_close(f.type)) close = 1;
       if (Emit) {
         const uint64_t at = (uint64_t)first + recs;
-        if (at < max_frames) {
-          uint4* dst = reinterpret_cast<uint4*>(frames + at);
+        if (at < a.max_frames) {
+          uint4* dst = reinterpret_cast<uint4*>(a.frames + at);
 #pragma unroll
           for (uint32_t q = 0; q < 3; ++q) {  // the record's three 16-B parts, spread over the group's lanes
             if (lane != q % kFrameLanes) continue;
@@ -231,63 +226,47 @@ __global__ __launch_bounds__(kFrameBlock) void mq_frames_kernel(
   }
   if (Emit || lane != 0) return;
   ws.counts[i] = recs;
-  if (i + 1 == max_pkts) ws.counts[max_pkts] = 0;
+  if (i + 1 == a.max_pkts) ws.counts[a.max_pkts] = 0;
   // first is written by the emit pass
   const uint4 s = make_uint4(0u, recs | err_pos << 16, pads | status << 16 | flags << 24, 0u);
-  *reinterpret_cast<uint4*>(summary + i) = s;
-  if (conn_flags && status != MQ_FRAMES_SKIPPED && status != MQ_ERR_INVALID_ARG && r.dgram < n_dgrams) {
-    const uint32_t c = dgrams[r.dgram].conn;
+  *reinterpret_cast<uint4*>(a.summary + i) = s;
+  if (a.conn_flags && status != MQ_FRAMES_SKIPPED && status != MQ_ERR_INVALID_ARG && r.dgram < a.n_dgrams) {
+    const uint32_t c = a.dgrams[r.dgram].conn;
     uint32_t bits = 0;
     if (status == MQ_OK && flags && r.level < 3) bits |= 1u << r.level;
     if (close) bits |= 1u << 3;
     if (status == MQ_ERR_FRAME) bits |= 1u << 4;
-    if (bits && c < n_conns) atomicOr(conn_flags + c, bits);
+    if (bits && c < a.n_conns) atomicOr(a.conn_flags + c, bits);
   }
 }
 
 // ---- host side -----------------------------------------------------------------------------------------
 namespace {
-size_t frames_al256(size_t b) { return (b + 255) & ~(size_t)255; }
-size_t frames_cub_bytes(uint32_t n) {
-  size_t b = 0;
-  (void)hipcub::DeviceScan::ExclusiveSum(nullptr, b, (const uint32_t*)nullptr, (uint32_t*)nullptr, (int)n + 1);
-  return b;
-}
-// workspace: [counts][first][scan scratch]
-size_t frames_layout(uint32_t n, void* base, FramesWs* w) {
-  size_t off = 0;
-  auto take = [&](size_t bytes) {
-    const size_t at = off;
-    off += frames_al256(bytes);
-    return base ? (uint8_t*)base + at : nullptr;
-  };
-  uint8_t* counts = take(4 * ((size_t)n + 1));
-  uint8_t* first = take(4 * ((size_t)n + 1));
-  const size_t cb = frames_cub_bytes(n);
-  uint8_t* cub = take(cb);
-  if (w) w->counts = (uint32_t*)counts, w->first = (uint32_t*)first, w->cub = cub, w->cub_bytes = cb;
-  return off;
+size_t frames_layout(uint32_t n, void* base, FramesWs& w) {
+  Carve c(base);
+  w.counts = c.take<uint32_t>((size_t)n + 1);
+  w.first = c.take<uint32_t>((size_t)n + 1);
+  w.cub_bytes = cub_temp_bytes<false>(0, 0, {n + 1});
+  w.cub = c.take<uint8_t>(w.cub_bytes);
+  return c.bytes();
 }
 }  // namespace
 
-size_t mq_frames_workspace(uint32_t max_pkts) { return frames_layout(max_pkts, nullptr, nullptr); }
+size_t mq_frames_workspace(uint32_t max_pkts) {
+  FramesWs w = {};
+  return frames_layout(max_pkts, nullptr, w);
+}
 
 // max_pkts > 0
-hipError_t mq_launch_frames(const uint8_t* arena, uint64_t arena_len, const mq_recv_pkt* pkts,
-                            const uint32_t* n_pkts_dev, uint32_t max_pkts, const mq_dgram* dgrams, uint32_t n_dgrams,
-                            mq_pkt_frames* summary, mq_frame* frames, uint32_t max_frames, uint32_t* n_frames,
-                            uint32_t* conn_flags, uint32_t n_conns, void* workspace, hipStream_t s) {
+hipError_t mq_launch_frames(const FramesArgs& a, void* workspace, hipStream_t s) {
   FramesWs w = {};
-  frames_layout(max_pkts, workspace, &w);
+  frames_layout(a.max_pkts, workspace, w);
   hipError_t e;
-  if (conn_flags && n_conns && (e = hipMemsetAsync(conn_flags, 0, 4 * (size_t)n_conns, s)) != hipSuccess) return e;
-  const dim3 grid((max_pkts + kFramePktsPerBlock - 1) / kFramePktsPerBlock), block(kFrameBlock);
-  hipLaunchKernelGGL(mq_frames_kernel<false>, grid, block, 0, s, arena, arena_len, pkts, n_pkts_dev, max_pkts, dgrams,
-                     n_dgrams, summary, frames, max_frames, n_frames, conn_flags, n_conns, w);
+  if (a.conn_flags && a.n_conns && (e = hipMemsetAsync(a.conn_flags, 0, 4 * (size_t)a.n_conns, s)) != hipSuccess) return e;
+  const dim3 grid((a.max_pkts + kFramePktsPerBlock - 1) / kFramePktsPerBlock), block(kFrameBlock);
+  hipLaunchKernelGGL(mq_frames_kernel<false>, grid, block, 0, s, a, w);
   if ((e = hipGetLastError()) != hipSuccess) return e;
-  size_t cb = w.cub_bytes;
-  if ((e = hipcub::DeviceScan::ExclusiveSum(w.cub, cb, w.counts, w.first, (int)max_pkts + 1, s)) != hipSuccess) return e;
-  hipLaunchKernelGGL(mq_frames_kernel<true>, grid, block, 0, s, arena, arena_len, pkts, n_pkts_dev, max_pkts, dgrams,
-                     n_dgrams, summary, frames, max_frames, n_frames, conn_flags, n_conns, w);
+  if ((e = exclusive_sum(w, w.counts, w.first, a.max_pkts + 1, s)) != hipSuccess) return e;
+  hipLaunchKernelGGL(mq_frames_kernel<true>, grid, block, 0, s, a, w);
   return hipGetLastError();
 }

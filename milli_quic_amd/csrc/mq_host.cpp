@@ -21,6 +21,7 @@
 #include "mq_resident.h"
 #include "mq_route.h"
 #include "mq_runtime.h"
+#include "mq_workspace.h"
 
 using mq::KeyRow;
 
@@ -913,8 +914,7 @@ void mq_keytable_free(mq_keytable* kt) {
 }
 
 // workspace: [open pre-pass HP masks, 8 B per packet][partition lists (mixed batches)]
-static size_t ws_align(size_t b) { return (b + 255) & ~(size_t)255; }
-size_t mq_batch_workspace_size(uint32_t n) { return ws_align(8 * (size_t)n) + mq_partition_workspace(n); }
+size_t mq_batch_workspace_size(uint32_t n) { return mq::al256(8 * (size_t)n) + mq_partition_workspace(n); }
 
 // recv_pass (mq_batch_recv's AEAD passes): descriptors without a valid key row are skipped —
 // no status is written for them; the receive composite reads only what it attempted. live (receive
@@ -962,7 +962,7 @@ static int batch(const mq::Switches& sw, bool open, const mq_keytable* kt, uint8
     // it exactly as the flat launch would.
     if (!ws || n > (1u << 30)) return MQ_ERR_INVALID_ARG;
     const bool aes_only = suite_hint == MQ_SUITE_AES128GCM;
-    uint8_t* pw = ws + ws_align(8 * (size_t)n);
+    uint8_t* pw = ws + mq::al256(8 * (size_t)n);
     uint32_t* list = (uint32_t*)pw;
     size_t codes_off, counts_off;
     mq_partition_layout(n, &codes_off, &counts_off);
@@ -1162,7 +1162,7 @@ int mq_batch_recv_rekey(mq_keytable* kt, mq_conn_recv* conns, uint32_t n_conns, 
 // ---- send composite from frames (transmit.rs:499-755) -----------------------------------------
 // workspace: [descriptors 32 B x n][build status n][seal workspace]
 size_t mq_batch_protect_workspace_size(uint32_t n) {
-  return ws_align(sizeof(mq_pkt_desc) * (size_t)n) + ws_align(n) + mq_batch_workspace_size(n);
+  return mq::al256(sizeof(mq_pkt_desc) * (size_t)n) + mq::al256(n) + mq_batch_workspace_size(n);
 }
 
 int mq_batch_protect(const mq_keytable* kt, const mq_conn_send* conns, uint32_t n_conns, const uint8_t* frames,
@@ -1187,8 +1187,8 @@ int mq_batch_protect(const mq_keytable* kt, const mq_conn_send* conns, uint32_t 
                : MQ_ERR_HIP;
   uint8_t* ws = (uint8_t*)workspace;
   mq_pkt_desc* desc = (mq_pkt_desc*)ws;
-  uint8_t* bstatus = ws + ws_align(sizeof(mq_pkt_desc) * (size_t)n);
-  void* seal_ws = bstatus + ws_align(n);
+  uint8_t* bstatus = ws + mq::al256(sizeof(mq_pkt_desc) * (size_t)n);
+  void* seal_ws = bstatus + mq::al256(n);
   // Pipelined (r04): the batch in kProtectChunks chunks, each built on the caller's stream and sealed
   // on a side stream once its build is done, so chunk k's seal (VALU-bound) runs beside chunk
   // k + 1's build (memory-bound). r03 built the whole batch, then sealed it: 1.35 + 1.14 ms at
@@ -1413,10 +1413,9 @@ int mq_batch_frames(const uint8_t* arena, uint64_t arena_len, const mq_recv_pkt*
       return MQ_ERR_HIP;
     return MQ_OK;
   }
-  return mq_launch_frames(arena, arena_len, pkts, n_pkts_dev, max_pkts, dgrams, n_dgrams, summary, frames, max_frames,
-                          n_frames, conn_flags, n_conns, workspace, s) == hipSuccess
-             ? MQ_OK
-             : MQ_ERR_HIP;
+  const mq::FramesArgs a = {arena,   arena_len, pkts,       n_pkts_dev, max_pkts,   dgrams, n_dgrams,
+                            summary, frames,    max_frames, n_frames,   conn_flags, n_conns};  // in FramesArgs' order
+  return mq_launch_frames(a, workspace, s) == hipSuccess ? MQ_OK : MQ_ERR_HIP;
 }
 
 // ---- received-PN trackers and ACK frames behind mq_batch_frames (mq_acks.hip) -------------------
@@ -1441,10 +1440,9 @@ int mq_batch_acks(const mq_recv_pkt* pkts, const uint32_t* n_pkts_dev, uint32_t 
   if (dev < 0) return MQ_ERR_NO_DEVICE;
   DeviceGuard g(dev);
   if (!g.ok()) return MQ_ERR_NO_DEVICE;
-  return mq_launch_acks(pkts, n_pkts_dev, max_pkts, summary, dgrams, n_dgrams, conn_flags, trackers, ack_pending,
-                        n_conns, build, workspace, (hipStream_t)stream) == hipSuccess
-             ? MQ_OK
-             : MQ_ERR_HIP;
+  const mq::AcksArgs a = {pkts,       n_pkts_dev, max_pkts,    summary, dgrams, n_dgrams,
+                          conn_flags, trackers,   ack_pending, n_conns, build};
+  return mq_launch_acks(a, workspace, (hipStream_t)stream) == hipSuccess ? MQ_OK : MQ_ERR_HIP;
 }
 
 // ---- stream bookkeeping and payload gather behind mq_batch_frames (mq_stream_data.hip) ----------
@@ -1477,11 +1475,10 @@ int mq_batch_stream_data(const uint8_t* arena, uint64_t arena_len, const mq_recv
   if (!g.ok()) return MQ_ERR_NO_DEVICE;
   hipStream_t s = (hipStream_t)stream;
   if (max_frames == 0 || n_conns == 0) return hipMemsetAsync(n_evts, 0, 4, s) == hipSuccess ? MQ_OK : MQ_ERR_HIP;
-  return mq_launch_stream_data(arena, arena_len, pkts, n_pkts_dev, max_pkts, dgrams, n_dgrams, frames, n_frames_dev,
-                               max_frames, streams, n_conns, bufs, stream_buf, initial_max_stream_data, flags, evts,
-                               n_evts, workspace, s) == hipSuccess
-             ? MQ_OK
-             : MQ_ERR_HIP;
+  const mq::StreamDataArgs a = {arena, arena_len, pkts, n_pkts_dev, max_pkts, dgrams, n_dgrams, frames, n_frames_dev,
+                                max_frames, streams, n_conns, bufs, stream_buf, initial_max_stream_data, flags, evts,
+                                n_evts};
+  return mq_launch_stream_data(a, workspace, s) == hipSuccess ? MQ_OK : MQ_ERR_HIP;
 }
 
 int mq_batch_stream_read(mq_conn_streams* streams, uint32_t n_conns, const uint8_t* bufs, uint32_t stream_buf,
@@ -1496,10 +1493,8 @@ int mq_batch_stream_read(mq_conn_streams* streams, uint32_t n_conns, const uint8
   DeviceGuard g(dev);
   if (!g.ok()) return MQ_ERR_NO_DEVICE;
   if (n_reqs == 0) return MQ_OK;
-  return mq_launch_stream_read(streams, n_conns, bufs, stream_buf, reqs, n_reqs, out, out_len, res, workspace,
-                               (hipStream_t)stream) == hipSuccess
-             ? MQ_OK
-             : MQ_ERR_HIP;
+  const mq::StreamReadArgs a = {streams, n_conns, bufs, stream_buf, reqs, n_reqs, out, out_len, res};
+  return mq_launch_stream_read(a, workspace, (hipStream_t)stream) == hipSuccess ? MQ_OK : MQ_ERR_HIP;
 }
 
 // ---- loss recovery behind mq_batch_protect and mq_batch_frames (mq_recovery.hip) -----------------

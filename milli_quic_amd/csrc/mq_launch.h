@@ -138,36 +138,68 @@ hipError_t mq_launch_cid_compact(const mq::CidTableDev& t, void* to, hipStream_t
 int mq_resident_call(int dev, const mq::ResReq& q, uint64_t uid, const uint8_t* aad, const uint8_t* body, uint8_t* out,
                      size_t out_off, size_t out_len, int* status, uint32_t* mask);
 
-// ---- mq_frames.hip ------------------------------------------------------------------------------
-size_t mq_frames_workspace(uint32_t max_pkts);
-hipError_t mq_launch_frames(const uint8_t* arena, uint64_t arena_len, const mq_recv_pkt* pkts,
-                            const uint32_t* n_pkts_dev, uint32_t max_pkts, const mq_dgram* dgrams, uint32_t n_dgrams,
-                            mq_pkt_frames* summary, mq_frame* frames, uint32_t max_frames, uint32_t* n_frames,
-                            uint32_t* conn_flags, uint32_t n_conns, void* workspace, hipStream_t s);
-
-// ---- mq_acks.hip --------------------------------------------------------------------------------
-size_t mq_acks_workspace(uint32_t max_pkts, uint32_t n_conns);
-hipError_t mq_launch_acks(const mq_recv_pkt* pkts, const uint32_t* n_pkts_dev, uint32_t max_pkts,
-                          const mq_pkt_frames* summary, const mq_dgram* dgrams, uint32_t n_dgrams,
-                          const uint32_t* conn_flags, mq_pn_tracker* trackers, uint32_t* ack_pending, uint32_t n_conns,
-                          const mq_ack_build* build, void* workspace, hipStream_t s);
-
-// ---- mq_stream_data.hip -------------------------------------------------------------------------
-size_t mq_stream_data_workspace(uint32_t max_frames, uint32_t n_conns);
-size_t mq_stream_read_workspace(uint32_t n_reqs, uint32_t n_conns);
-hipError_t mq_launch_stream_data(const uint8_t* arena, uint64_t arena_len, const mq_recv_pkt* pkts,
-                                 const uint32_t* n_pkts_dev, uint32_t max_pkts, const mq_dgram* dgrams,
-                                 uint32_t n_dgrams, const mq_frame* frames, const uint32_t* n_frames_dev,
-                                 uint32_t max_frames, mq_conn_streams* streams, uint32_t n_conns, uint8_t* bufs,
-                                 uint32_t stream_buf, uint64_t initial_max_stream_data, uint32_t flags,
-                                 mq_stream_evt* evts, uint32_t* n_evts, void* workspace, hipStream_t s);
-hipError_t mq_launch_stream_read(mq_conn_streams* streams, uint32_t n_conns, const uint8_t* bufs, uint32_t stream_buf,
-                                 const mq_stream_read_req* reqs, uint32_t n_reqs, uint8_t* out, uint64_t out_len,
-                                 mq_stream_read_res* res, void* workspace, hipStream_t s);
-
-// ---- mq_recovery.hip ----------------------------------------------------------------------------
+// ---- mq_frames.hip, mq_acks.hip, mq_stream_data.hip, mq_recovery.hip ------------------------------
 namespace mq {
-// mq_batch_sent's and mq_batch_recovery's arguments as they arrive, checked by mq_host.cpp
+// The entry points' arguments as they arrive, checked by mq_host.cpp; the kernels take them by value.
+struct FramesArgs {
+  const uint8_t* arena;
+  uint64_t arena_len;
+  const mq_recv_pkt* pkts;
+  const uint32_t* n_pkts_dev;
+  uint32_t max_pkts;
+  const mq_dgram* dgrams;
+  uint32_t n_dgrams;
+  mq_pkt_frames* summary;
+  mq_frame* frames;
+  uint32_t max_frames;
+  uint32_t* n_frames;
+  uint32_t* conn_flags;
+  uint32_t n_conns;
+};
+struct AcksArgs {
+  const mq_recv_pkt* pkts;
+  const uint32_t* n_pkts_dev;
+  uint32_t max_pkts;
+  const mq_pkt_frames* summary;
+  const mq_dgram* dgrams;
+  uint32_t n_dgrams;
+  const uint32_t* conn_flags;
+  mq_pn_tracker* trackers;
+  uint32_t* ack_pending;
+  uint32_t n_conns;
+  const mq_ack_build* build;  // host pointer
+};
+struct StreamDataArgs {
+  const uint8_t* arena;
+  uint64_t arena_len;
+  const mq_recv_pkt* pkts;
+  const uint32_t* n_pkts_dev;
+  uint32_t max_pkts;
+  const mq_dgram* dgrams;
+  uint32_t n_dgrams;
+  const mq_frame* frames;
+  const uint32_t* n_frames_dev;
+  uint32_t max_frames;
+  mq_conn_streams* streams;
+  uint32_t n_conns;
+  uint8_t* bufs;
+  uint32_t stream_buf;
+  uint64_t initial_max_stream_data;
+  uint32_t flags;
+  mq_stream_evt* evts;
+  uint32_t* n_evts;
+};
+struct StreamReadArgs {
+  mq_conn_streams* streams;
+  uint32_t n_conns;
+  const uint8_t* bufs;
+  uint32_t stream_buf;
+  const mq_stream_read_req* reqs;
+  uint32_t n_reqs;
+  uint8_t* out;
+  uint64_t out_len;
+  mq_stream_read_res* res;
+};
 struct SentArgs {
   const mq_send_req* reqs;
   const uint8_t* status;
@@ -202,8 +234,16 @@ struct RecoveryArgs {
   uint32_t flags;
 };
 }  // namespace mq
+size_t mq_frames_workspace(uint32_t max_pkts);
+size_t mq_acks_workspace(uint32_t max_pkts, uint32_t n_conns);
+size_t mq_stream_data_workspace(uint32_t max_frames, uint32_t n_conns);
+size_t mq_stream_read_workspace(uint32_t n_reqs, uint32_t n_conns);
 size_t mq_sent_workspace(uint32_t n, uint32_t n_conns);
 size_t mq_recovery_workspace(uint32_t max_frames, uint32_t n_conns);
+hipError_t mq_launch_frames(const mq::FramesArgs& a, void* workspace, hipStream_t s);  // max_pkts > 0
+hipError_t mq_launch_acks(const mq::AcksArgs& a, void* workspace, hipStream_t s);
+hipError_t mq_launch_stream_data(const mq::StreamDataArgs& a, void* workspace, hipStream_t s);
+hipError_t mq_launch_stream_read(const mq::StreamReadArgs& a, void* workspace, hipStream_t s);
 hipError_t mq_launch_sent(const mq::SentArgs& a, void* workspace, hipStream_t s);
 hipError_t mq_launch_recovery(const mq::RecoveryArgs& a, void* workspace, hipStream_t s);
 

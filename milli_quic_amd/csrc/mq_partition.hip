@@ -30,6 +30,7 @@
 // pass, ~126 us per mixed 2^20-packet partition.)
 #include "mq_tile.h"
 #include "mq_launch.h"
+#include "mq_workspace.h"
 
 #include <cstdlib>
 
@@ -641,7 +642,7 @@ static bool keyed_layout(uint32_t n, uint32_t n_rows) {
 
 // list (2 x cap entries) | codes (8 B per packet, the count kernel's) |
 // meta (2 totals, hot row, hot segment entries, kClasses segment starts) | keyed bins, 256-B aligned pieces
-static size_t part_align(size_t b) { return (b + 255) & ~(size_t)255; }
+// (al256). The caller (mq_host.cpp) places the pieces by mq_partition_layout.
 
 // The per-row segments of a keyed partition (rowseg, 2 words per row, keyed_ws), or null when
 // mq_launch_partition(n, n_rows) does not lay the list out keyed. counts: the partition's meta (as
@@ -649,7 +650,7 @@ static size_t part_align(size_t b) { return (b + 255) & ~(size_t)255; }
 bool mq_partition_keyed(uint32_t n, uint32_t n_rows) { return keyed_layout(n, n_rows); }
 const uint32_t* mq_partition_rowseg(uint32_t n, uint32_t n_rows, const uint32_t* counts) {
   if (!keyed_layout(n, n_rows)) return nullptr;
-  return keyed_ws((uint32_t*)((uint8_t*)counts + part_align(sizeof(uint32_t) * kMetaWords)), n_rows).rowseg;
+  return keyed_ws((uint32_t*)((uint8_t*)counts + al256(sizeof(uint32_t) * kMetaWords)), n_rows).rowseg;
 }
 
 hipError_t mq_launch_partition(const mq::BatchArgs& b, uint32_t n, uint32_t* list, uint32_t* codes, uint32_t* counts,
@@ -670,7 +671,7 @@ hipError_t mq_launch_partition(const mq::BatchArgs& b, uint32_t n, uint32_t* lis
   uint32_t* cmax = counts + kMetaCmax;
   uint32_t* cls = counts + kMetaCls;
   uint32_t* reg = counts + kMetaReg;
-  uint32_t* bins = keyed_layout(n, n_rows) ? (uint32_t*)((uint8_t*)counts + part_align(sizeof(uint32_t) * kMetaWords))
+  uint32_t* bins = keyed_layout(n, n_rows) ? (uint32_t*)((uint8_t*)counts + al256(sizeof(uint32_t) * kMetaWords))
                                            : nullptr;
   const uint32_t list_q = cap / 2, bins_q = bins ? (uint32_t)keyed_zero_quads(n_rows) : 0u;  // 16-B words
   const uint32_t init_blocks = max(1u, min(256u, (list_q + bins_q + kPartThreads - 1) / kPartThreads));
@@ -696,15 +697,15 @@ const uint32_t* mq_partition_regions(const uint32_t* counts) { return counts + k
 
 size_t mq_partition_workspace(uint32_t n) {
   // keyed words (keyed_ws): 19 per row, rows <= key_bins(n) / 16, then btot and base
-  return part_align(sizeof(uint32_t) * 2 * (size_t)mq_partition_list_cap(n)) +
-         part_align(sizeof(uint2) * (size_t)n) + part_align(sizeof(uint32_t) * kMetaWords) +
-         part_align(sizeof(uint32_t) * (key_bins(n) / 16 * 19 + kRowBlocksMax + 8));
+  return al256(sizeof(uint32_t) * 2 * (size_t)mq_partition_list_cap(n)) +
+         al256(sizeof(uint2) * (size_t)n) + al256(sizeof(uint32_t) * kMetaWords) +
+         al256(sizeof(uint32_t) * (key_bins(n) / 16 * 19 + kRowBlocksMax + 8));
 }
 
 // offsets of the pieces inside the partition workspace
 void mq_partition_layout(uint32_t n, size_t* codes_off, size_t* counts_off) {
-  *codes_off = part_align(sizeof(uint32_t) * 2 * (size_t)mq_partition_list_cap(n));
-  *counts_off = *codes_off + part_align(sizeof(uint2) * (size_t)n);
+  *codes_off = al256(sizeof(uint32_t) * 2 * (size_t)mq_partition_list_cap(n));
+  *counts_off = *codes_off + al256(sizeof(uint2) * (size_t)n);
 }
 
 #ifdef MQ_STAMPS

@@ -28,11 +28,9 @@
 //   scan     exclusive sum of the events' loss counts: lost_first
 //   finish   one thread per event: lost_first, and its staged mq_lost_pkt to their place below max_lost
 // Every output is a function of the inputs: no atomics.
-#include <hipcub/hipcub.hpp>
-
-#include "mq_device.h"
 #include "mq_launch.h"
 #include "mq_recovery.h"
+#include "mq_replay.h"
 
 namespace mq {
 
@@ -54,13 +52,11 @@ static_assert(MQ_SENT_SLOTS == kSentSlots && MQ_SENT_USED == kSentUsed && MQ_SEN
                   MQ_ACKEVT_RANGES_BROKE == kEvtRangesBroke && MQ_ACKEVT_LOST_CUT == kEvtLostCut,
               "ABI constants");
 
-struct SentWs {
-  uint32_t *keys_in, *keys, *idx_in, *idx;  // n each
+struct SentWs : SortWs {  // n each
   void* cub;
   size_t cub_bytes;
 };
-struct RecoveryWs {
-  uint32_t *keys_in, *keys, *idx_in, *idx;  // max_frames each
+struct RecoveryWs : SortWs {                // max_frames each
   uint32_t *flags, *pos;                    // max_frames + 1: selected ACK records, their exclusive scan
   uint64_t *src, *now;                      // max_frames: arena offset of the range bytes, the datagram's time
   uint32_t *n_lost, *lost_base;             // max_frames + 1: losses per event, their exclusive scan
@@ -70,13 +66,8 @@ struct RecoveryWs {
   size_t cub_bytes;
 };
 
-// ---- the wave ----------------------------------------------------------------------------------------------
-__device__ __forceinline__ uint32_t rc_get32(uint32_t v, uint32_t src) {
-  return (uint32_t)__shfl((int)v, (int)(src & 63u), kWave);
-}
-__device__ __forceinline__ uint64_t rc_get64(uint64_t v, uint32_t src) {
-  return rc_get32((uint32_t)v, src) | (uint64_t)rc_get32((uint32_t)(v >> 32), src) << 32;
-}
+// ---- the wave: the group's ballot, get, below and count, and what only this file needs -------------------
+using RcLanes = LaneGroup<kWave>;
 // the value of lane `src`, which is the same in all lanes
 __device__ __forceinline__ uint32_t rc_bcast32(uint32_t v, uint32_t src) {
   return (uint32_t)__builtin_amdgcn_readlane((int)v, (int)(src & 63u));
@@ -103,12 +94,6 @@ __device__ __forceinline__ uint64_t rc_sum64(uint64_t v) {
   for (uint32_t d = kWave / 2; d; d >>= 1) v += rc_xor64(v, d);
   return v;
 }
-__device__ __forceinline__ uint64_t rc_ballot(bool p) { return __builtin_amdgcn_ballot_w64(p); }
-// set bits of the mask below this lane
-__device__ __forceinline__ uint32_t rc_below(uint64_t mask) {
-  return __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
-}
-__device__ __forceinline__ uint32_t rc_count(uint64_t mask) { return (uint32_t)__builtin_popcountll(mask); }
 // the lowest slot of a mask pair (low half, high half); one of them is not empty
 __device__ __forceinline__ uint32_t rc_first(uint64_t lo, uint64_t hi) {
   return lo ? (uint32_t)__builtin_ctzll(lo) : kWave + (uint32_t)__builtin_ctzll(hi);
@@ -178,13 +163,13 @@ struct LaneConn {
   // drop_space on both structures (recovery.rs:162-171, loss.rs:283-288)
   __device__ __forceinline__ void drop(uint32_t level) {
     const bool d0 = sent_is(meta[0], level), d1 = sent_is(meta[1], level);
-    s.count -= rc_count(rc_ballot(d0)) + rc_count(rc_ballot(d1));
+    s.count -= RcLanes::count(RcLanes::ballot(d0)) + RcLanes::count(RcLanes::ballot(d1));
     if (d0) clear(0);
     if (d1) clear(1);
     rec_drop_space(s, level);
   }
   __device__ __forceinline__ uint64_t timeout() const {
-    const bool any = rc_ballot(sent_counts_for_pto(meta[0]) || sent_counts_for_pto(meta[1])) != 0;
+    const bool any = RcLanes::ballot(sent_counts_for_pto(meta[0]) || sent_counts_for_pto(meta[1])) != 0;
     return rec_next_timeout(s, any);
   }
 };
@@ -208,22 +193,11 @@ struct LaneMark {
   }
 };
 
-// the run of key c in the ascending keys[0, n): [lower bound of c, lower bound of c + 1)
+// key_run for a key that the whole wave shares: the run's ends are scalars
 __device__ __forceinline__ void rc_run(const uint32_t* __restrict__ keys, uint32_t n, uint32_t c, uint32_t& r,
                                        uint32_t& r_end) {
-  uint32_t lo = 0, hi = n;
-  while (lo < hi) {
-    const uint32_t mid = lo + (hi - lo) / 2;
-    if (keys[mid] < c) lo = mid + 1;
-    else hi = mid;
-  }
-  r = lo, hi = n;
-  while (lo < hi) {
-    const uint32_t mid = lo + (hi - lo) / 2;
-    if (keys[mid] <= c) lo = mid + 1;
-    else hi = mid;
-  }
-  r = __builtin_amdgcn_readfirstlane(r), r_end = __builtin_amdgcn_readfirstlane(lo);
+  key_run(keys, n, c, r, r_end);
+  r = __builtin_amdgcn_readfirstlane(r), r_end = __builtin_amdgcn_readfirstlane(r_end);
 }
 
 }  // namespace mq
@@ -264,19 +238,19 @@ __global__ __launch_bounds__(kRcBlock) void mq_sent_replay_kernel(const mq_send_
       my_pn = reqs[i].pn, my_level = reqs[i].level, my_len = pkt_len[i], my_now = now[i];
     }
     // the k-th free slot takes the chunk's k-th request
-    const uint64_t f_lo = rc_ballot(!sent_used(t.meta[0])), f_hi = rc_ballot(!sent_used(t.meta[1]));
-    const uint32_t n_free = rc_count(f_lo) + rc_count(f_hi);
-    const uint32_t rank[2] = {rc_below(f_lo), rc_count(f_lo) + rc_below(f_hi)};
+    const uint64_t f_lo = RcLanes::ballot(!sent_used(t.meta[0])), f_hi = RcLanes::ballot(!sent_used(t.meta[1]));
+    const uint32_t n_free = RcLanes::count(f_lo) + RcLanes::count(f_hi);
+    const uint32_t rank[2] = {RcLanes::below(f_lo), RcLanes::count(f_lo) + RcLanes::below(f_hi)};
 #pragma unroll
     for (uint32_t h = 0; h < 2; ++h) {
-      const uint64_t q_pn = rc_get64(my_pn, rank[h]), q_now = rc_get64(my_now, rank[h]);
-      const uint32_t q_level = rc_get32(my_level, rank[h]), q_len = rc_get32(my_len, rank[h]);
+      const uint64_t q_pn = RcLanes::get64(my_pn, rank[h]), q_now = RcLanes::get64(my_now, rank[h]);
+      const uint32_t q_level = RcLanes::get32(my_level, rank[h]), q_len = RcLanes::get32(my_len, rank[h]);
       if (!sent_used(t.meta[h]) && rank[h] < cnt) t.pn[h] = q_pn, t.ts[h] = q_now, t.meta[h] = sent_new_meta(q_len, q_level);
     }
     t.s.count += n_free < cnt ? n_free : cnt;
     t.s.in_flight += rc_sum64(my_len);
     for (uint32_t l = 0; l < 3; ++l) {  // on_ack_eliciting_sent: the level's last request of the chunk
-      const uint64_t m = rc_ballot(my_level == l);
+      const uint64_t m = RcLanes::ballot(my_level == l);
       if (m) {
         t.s.last_sent[l] = rc_bcast64(my_now, 63u - (uint32_t)__builtin_clzll(m));
         t.s.have |= kHaveLastSent << l;
@@ -307,20 +281,12 @@ __global__ __launch_bounds__(kRcBlock) void mq_recovery_select_kernel(RecoveryAr
     const uint4 f = reinterpret_cast<const uint4*>(a.frames + k)[0];  // pkt; pos, len; type, level, data_pos; data_len, aux
     const uint32_t type = f.z & 0xFFu, level = (f.z >> 8) & 0xFFu, data_pos = f.z >> 16, data_len = f.w & 0xFFFFu;
     const bool ack = type == 0x02 || type == 0x03;
-    if ((ack || (type == 0x1e && (a.flags & MQ_RECOVERY_CLIENT))) && level < 3 && f.x < n_pkts) {
-      const uint4 p = reinterpret_cast<const uint4*>(a.pkts + f.x)[0];  // offset, pn
-      const uint4 b = reinterpret_cast<const uint4*>(a.pkts + f.x)[1];  // len, dgram, payload_offset + level + status, ..
-      if (b.y < a.n_dgrams) {
-        const uint32_t c = a.dgrams[b.y].conn;
-        const uint64_t off = p.x | (uint64_t)p.y << 32;
-        const uint32_t rel = (b.z & 0xFFFFu) + data_pos;
-        // no wrap: the sum is compared piece by piece
-        const bool inside = !ack || (off <= a.arena_len && rel <= a.arena_len - off && data_len <= a.arena_len - off - rel);
-        if (c < a.n_conns && inside) {
-          key = c, flag = ack;
-          src = off + rel;
-          if (ack) now = a.dgram_now[b.y];
-        }
+    if ((ack || (type == 0x1e && (a.flags & MQ_RECOVERY_CLIENT))) && level < 3) {
+      const FrameSite site = frame_site(a.pkts, n_pkts, a.dgrams, a.n_dgrams, a.arena_len, f.x, data_pos, data_len, ack);
+      if (site.conn < a.n_conns && site.inside) {
+        key = site.conn, flag = ack;
+        src = site.src;
+        if (ack) now = a.dgram_now[site.dgram];
       }
     }
   }
@@ -382,13 +348,13 @@ __global__ __launch_bounds__(kRcBlock) void mq_recovery_replay_kernel(RecoveryAr
       LaneMark mark = {t.pn[0], t.pn[1], sent_is(t.meta[0], level), sent_is(t.meta[1], level), false, false};
       uint32_t ev_flags = rec_walk_ranges(bytes, len, largest, first_range, mark);
       // 2. remove them; the first 32 in slot order are newly_acked
-      const uint64_t a_lo = rc_ballot(mark.a0), a_hi = rc_ballot(mark.a1);
-      const uint32_t n_acked = rc_count(a_lo) + rc_count(a_hi);
+      const uint64_t a_lo = RcLanes::ballot(mark.a0), a_hi = RcLanes::ballot(mark.a1);
+      const uint32_t n_acked = RcLanes::count(a_lo) + RcLanes::count(a_hi);
       uint64_t top_pn = 0, top_ts = 0;
       if (n_acked) {
         const uint64_t v0 = mark.a0 ? t.pn[0] : 0, v1 = mark.a1 ? t.pn[1] : 0;
         top_pn = rc_max64(v0 > v1 ? v0 : v1);
-        const uint32_t top = rc_first(rc_ballot(mark.a0 && t.pn[0] == top_pn), rc_ballot(mark.a1 && t.pn[1] == top_pn));
+        const uint32_t top = rc_first(RcLanes::ballot(mark.a0 && t.pn[0] == top_pn), RcLanes::ballot(mark.a1 && t.pn[1] == top_pn));
         top_ts = t.ts_of(top);
       }
       // 3. largest acked
@@ -420,19 +386,19 @@ __global__ __launch_bounds__(kRcBlock) void mq_recovery_replay_kernel(RecoveryAr
       const uint64_t delay = rec_loss_delay(t.s), lost_send_time = rec_sat_sub(now, delay);
       const uint32_t cls0 = sent_is(t.meta[0], level) ? rec_loss_class(t.pn[0], t.ts[0], la, lost_send_time) : kLossSkip;
       const uint32_t cls1 = sent_is(t.meta[1], level) ? rec_loss_class(t.pn[1], t.ts[1], la, lost_send_time) : kLossSkip;
-      uint64_t l_lo = rc_ballot(cls0 == kLossLost), l_hi = rc_ballot(cls1 == kLossLost);
+      uint64_t l_lo = RcLanes::ballot(cls0 == kLossLost), l_hi = RcLanes::ballot(cls1 == kLossLost);
       uint32_t stop = kSentSlots;  // the slot of the 65th loss: the scan ends there
-      if (rc_count(l_lo) + rc_count(l_hi) > kRecLostMax) {
-        const uint32_t rank0 = rc_below(l_lo), rank1 = rc_count(l_lo) + rc_below(l_hi);
-        stop = rc_first(rc_ballot(cls0 == kLossLost && rank0 == kRecLostMax),
-                        rc_ballot(cls1 == kLossLost && rank1 == kRecLostMax));
-        l_lo = rc_ballot(cls0 == kLossLost && rank0 < kRecLostMax);
-        l_hi = rc_ballot(cls1 == kLossLost && rank1 < kRecLostMax);
+      if (RcLanes::count(l_lo) + RcLanes::count(l_hi) > kRecLostMax) {
+        const uint32_t rank0 = RcLanes::below(l_lo), rank1 = RcLanes::count(l_lo) + RcLanes::below(l_hi);
+        stop = rc_first(RcLanes::ballot(cls0 == kLossLost && rank0 == kRecLostMax),
+                        RcLanes::ballot(cls1 == kLossLost && rank1 == kRecLostMax));
+        l_lo = RcLanes::ballot(cls0 == kLossLost && rank0 < kRecLostMax);
+        l_hi = RcLanes::ballot(cls1 == kLossLost && rank1 < kRecLostMax);
         ev_flags |= kEvtLostCut;
       }
       const bool w0 = cls0 == kLossWait && t.lane < stop, w1 = cls1 == kLossWait && t.lane + kWave < stop;
       uint64_t loss_time = kRecNone;
-      if (rc_ballot(w0 || w1)) {
+      if (RcLanes::ballot(w0 || w1)) {
         const uint64_t d0 = w0 ? t.ts[0] + delay : kRecNone, d1 = w1 ? t.ts[1] + delay : kRecNone;
         loss_time = rc_min64(d0 < d1 ? d0 : d1);
       }
@@ -445,8 +411,8 @@ __global__ __launch_bounds__(kRcBlock) void mq_recovery_replay_kernel(RecoveryAr
         if (l_lo) l_lo &= l_lo - 1;
         else l_hi &= l_hi - 1;
         const uint64_t pn = t.pn_of(from);
-        const uint64_t m_lo = rc_ballot(sent_is(t.meta[0], level) && t.pn[0] == pn);
-        const uint64_t m_hi = rc_ballot(sent_is(t.meta[1], level) && t.pn[1] == pn);
+        const uint64_t m_lo = RcLanes::ballot(sent_is(t.meta[0], level) && t.pn[0] == pn);
+        const uint64_t m_hi = RcLanes::ballot(sent_is(t.meta[1], level) && t.pn[1] == pn);
         if (!(m_lo | m_hi)) continue;  // remove() found nothing
         const uint32_t slot = rc_first(m_lo, m_hi);  // the first entry with this pn, not always `from`
         const uint32_t size = sent_size(t.meta_of(slot));
@@ -494,81 +460,57 @@ __global__ __launch_bounds__(kRcBlock) void mq_recovery_finish_kernel(RecoveryAr
 
 // ---- host side -----------------------------------------------------------------------------------------
 namespace {
-size_t rc_al256(size_t b) { return (b + 255) & ~(size_t)255; }
-uint32_t rc_key_bits(uint32_t n_conns) {  // the keys are 0 .. n_conns
-  uint32_t bits = 1;
-  while (bits < 32 && ((uint64_t)n_conns >> bits)) ++bits;
-  return bits;
+// Both layouts end with 256 bytes that no kernel touches. Nobody knows why they are there; callers size
+// by these figures.
+size_t sent_layout(uint32_t n, uint32_t n_conns, void* base, SentWs& w) {
+  Carve c(base);
+  w.keys_in = c.take<uint32_t>(n);
+  w.keys = c.take<uint32_t>(n);
+  w.idx_in = c.take<uint32_t>(n);
+  w.idx = c.take<uint32_t>(n);
+  w.cub_bytes = cub_temp_bytes<true>(n, key_bits(n_conns), {});
+  w.cub = c.take<uint8_t>(w.cub_bytes);
+  return c.bytes() + 256;
 }
-size_t rc_cub_bytes(uint32_t n, uint32_t n_conns, bool scan) {
-  size_t a = 0, b = 0;
-  (void)hipcub::DeviceRadixSort::SortPairs(nullptr, a, (const uint32_t*)nullptr, (uint32_t*)nullptr,
-                                           (const uint32_t*)nullptr, (uint32_t*)nullptr, (int)n, 0,
-                                           (int)rc_key_bits(n_conns));
-  if (scan) (void)hipcub::DeviceScan::ExclusiveSum(nullptr, b, (const uint32_t*)nullptr, (uint32_t*)nullptr, (int)n + 1);
-  return a > b ? a : b;
-}
-struct Taker {
-  void* base;
-  size_t off = 0;
-  uint8_t* operator()(size_t bytes) {
-    const size_t at = off;
-    off += rc_al256(bytes);
-    return base ? (uint8_t*)base + at : nullptr;
-  }
-};
-size_t sent_layout(uint32_t n, uint32_t n_conns, void* base, SentWs* w) {
-  Taker take{base};
-  uint8_t* p[4];
-  for (int q = 0; q < 4; ++q) p[q] = take(4 * (size_t)n);
-  const size_t cb = rc_cub_bytes(n, n_conns, false);
-  uint8_t* cub = take(cb);
-  if (w) {
-    w->keys_in = (uint32_t*)p[0], w->keys = (uint32_t*)p[1], w->idx_in = (uint32_t*)p[2], w->idx = (uint32_t*)p[3];
-    w->cub = cub, w->cub_bytes = cb;
-  }
-  return take.off + 256;
-}
-size_t recovery_layout(uint32_t n, uint32_t n_conns, void* base, RecoveryWs* w) {
-  Taker take{base};
-  uint8_t* p[12];
-  for (int q = 0; q < 4; ++q) p[q] = take(4 * (size_t)n);
-  for (int q = 4; q < 6; ++q) p[q] = take(4 * ((size_t)n + 1));
-  for (int q = 6; q < 8; ++q) p[q] = take(8 * (size_t)n);
-  for (int q = 8; q < 10; ++q) p[q] = take(4 * ((size_t)n + 1));
-  p[10] = take(4 * (size_t)n);
-  p[11] = take(sizeof(mq_lost_pkt) * (size_t)kSentSlots * n_conns);
-  const size_t cb = rc_cub_bytes(n, n_conns, true);
-  uint8_t* cub = take(cb);
-  if (w) {
-    w->keys_in = (uint32_t*)p[0], w->keys = (uint32_t*)p[1], w->idx_in = (uint32_t*)p[2], w->idx = (uint32_t*)p[3];
-    w->flags = (uint32_t*)p[4], w->pos = (uint32_t*)p[5], w->src = (uint64_t*)p[6], w->now = (uint64_t*)p[7];
-    w->n_lost = (uint32_t*)p[8], w->lost_base = (uint32_t*)p[9], w->lost_at = (uint32_t*)p[10];
-    w->staged = (mq_lost_pkt*)p[11];
-    w->cub = cub, w->cub_bytes = cb;
-  }
-  return take.off + 256;
+size_t recovery_layout(uint32_t n, uint32_t n_conns, void* base, RecoveryWs& w) {
+  Carve c(base);
+  w.keys_in = c.take<uint32_t>(n);
+  w.keys = c.take<uint32_t>(n);
+  w.idx_in = c.take<uint32_t>(n);
+  w.idx = c.take<uint32_t>(n);
+  w.flags = c.take<uint32_t>((size_t)n + 1);
+  w.pos = c.take<uint32_t>((size_t)n + 1);
+  w.src = c.take<uint64_t>(n);
+  w.now = c.take<uint64_t>(n);
+  w.n_lost = c.take<uint32_t>((size_t)n + 1);
+  w.lost_base = c.take<uint32_t>((size_t)n + 1);
+  w.lost_at = c.take<uint32_t>(n);
+  w.staged = c.take<mq_lost_pkt>((size_t)kSentSlots * n_conns);
+  w.cub_bytes = cub_temp_bytes<true>(n, key_bits(n_conns), {n + 1});
+  w.cub = c.take<uint8_t>(w.cub_bytes);
+  return c.bytes() + 256;
 }
 dim3 rc_blocks(uint64_t threads) { return dim3((uint32_t)((threads + kRcBlock - 1) / kRcBlock)); }
 }  // namespace
 
-size_t mq_sent_workspace(uint32_t n, uint32_t n_conns) { return sent_layout(n, n_conns, nullptr, nullptr); }
+size_t mq_sent_workspace(uint32_t n, uint32_t n_conns) {
+  SentWs w = {};
+  return sent_layout(n, n_conns, nullptr, w);
+}
 size_t mq_recovery_workspace(uint32_t max_frames, uint32_t n_conns) {
-  return recovery_layout(max_frames, n_conns, nullptr, nullptr);
+  RecoveryWs w = {};
+  return recovery_layout(max_frames, n_conns, nullptr, w);
 }
 
 // n > 0 and n_conns > 0
 hipError_t mq_launch_sent(const SentArgs& a, void* workspace, hipStream_t s) {
   SentWs w = {};
-  sent_layout(a.n, a.n_conns, workspace, &w);
+  sent_layout(a.n, a.n_conns, workspace, w);
   hipError_t e;
   const dim3 block(kRcBlock);
   hipLaunchKernelGGL(mq_sent_key_kernel, rc_blocks(a.n), block, 0, s, a.reqs, a.status, a.n, a.n_conns, w);
   if ((e = hipGetLastError()) != hipSuccess) return e;
-  size_t cb = w.cub_bytes;
-  if ((e = hipcub::DeviceRadixSort::SortPairs(w.cub, cb, w.keys_in, w.keys, w.idx_in, w.idx, (int)a.n, 0,
-                                              (int)rc_key_bits(a.n_conns), s)) != hipSuccess)
-    return e;
+  if ((e = sort_by_key(w, a.n, key_bits(a.n_conns), s)) != hipSuccess) return e;
   hipLaunchKernelGGL(mq_sent_replay_kernel, rc_blocks((uint64_t)a.n_conns * kWave), block, 0, s, a.reqs, a.pkt_len, a.now,
                      a.n, a.rec, a.n_conns, a.timeouts, w);
   return hipGetLastError();
@@ -577,18 +519,14 @@ hipError_t mq_launch_sent(const SentArgs& a, void* workspace, hipStream_t s) {
 // n_conns > 0; max_frames == 0 applies the drop mask alone
 hipError_t mq_launch_recovery(const RecoveryArgs& a, void* workspace, hipStream_t s) {
   RecoveryWs w = {};
-  recovery_layout(a.max_frames, a.n_conns, workspace, &w);
+  recovery_layout(a.max_frames, a.n_conns, workspace, w);
   hipError_t e;
   const dim3 block(kRcBlock);
   if (a.max_frames) {
     hipLaunchKernelGGL(mq_recovery_select_kernel, rc_blocks((uint64_t)a.max_frames + 1), block, 0, s, a, w);
     if ((e = hipGetLastError()) != hipSuccess) return e;
-    size_t cb = w.cub_bytes;
-    if ((e = hipcub::DeviceScan::ExclusiveSum(w.cub, cb, w.flags, w.pos, (int)a.max_frames + 1, s)) != hipSuccess) return e;
-    cb = w.cub_bytes;
-    if ((e = hipcub::DeviceRadixSort::SortPairs(w.cub, cb, w.keys_in, w.keys, w.idx_in, w.idx, (int)a.max_frames, 0,
-                                                (int)rc_key_bits(a.n_conns), s)) != hipSuccess)
-      return e;
+    if ((e = exclusive_sum(w, w.flags, w.pos, a.max_frames + 1, s)) != hipSuccess) return e;
+    if ((e = sort_by_key(w, a.max_frames, key_bits(a.n_conns), s)) != hipSuccess) return e;
   } else {
     if ((e = hipMemsetAsync(a.n_evts, 0, 4, s)) != hipSuccess) return e;
     if ((e = hipMemsetAsync(a.n_lost, 0, 4, s)) != hipSuccess) return e;
@@ -597,9 +535,7 @@ hipError_t mq_launch_recovery(const RecoveryArgs& a, void* workspace, hipStream_
   hipLaunchKernelGGL(mq_recovery_replay_kernel, rc_blocks((uint64_t)a.n_conns * kWave), block, 0, s, a, w);
   if ((e = hipGetLastError()) != hipSuccess) return e;
   if (!a.max_frames) return hipSuccess;
-  size_t cb = w.cub_bytes;
-  if ((e = hipcub::DeviceScan::ExclusiveSum(w.cub, cb, w.n_lost, w.lost_base, (int)a.max_frames + 1, s)) != hipSuccess)
-    return e;
+  if ((e = exclusive_sum(w, w.n_lost, w.lost_base, a.max_frames + 1, s)) != hipSuccess) return e;
   hipLaunchKernelGGL(mq_recovery_finish_kernel, rc_blocks(a.max_frames), block, 0, s, a, w);
   return hipGetLastError();
 }

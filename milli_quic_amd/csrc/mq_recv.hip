@@ -28,6 +28,7 @@
 
 #include "mq_device.h"
 #include "mq_launch.h"
+#include "mq_workspace.h"
 
 using namespace mq;
 
@@ -919,8 +920,6 @@ extern "C" __global__ __launch_bounds__(kSortThreads) void mq_sort_scatter_kerne
 
 // ---- launch helpers ------------------------------------------------------------------------------
 namespace {
-size_t al(size_t b) { return (b + 255) & ~(size_t)255; }
-
 struct RecvWs {
   uint32_t *counts, *base, *total, *keys, *vals, *skeys, *svals, *seg_lo, *seg_hi, *attempts;
   uint32_t *shist, *tkeys, *tvals;  // the sort's digit histograms and ping-pong buffers
@@ -951,41 +950,40 @@ size_t cub_bytes(uint32_t n_dgrams, uint32_t max_pkts) {
 
 RecvWs layout(uint8_t* p, uint32_t n_dgrams, uint32_t max_pkts, uint32_t n_conns, size_t open_ws_bytes) {
   RecvWs w;
-  size_t o = 0;
-  auto take = [&](size_t bytes) { uint8_t* q = p ? p + o : nullptr; o += al(bytes); return q; };
-  w.counts = (uint32_t*)take(4ull * n_dgrams + 4);
-  w.base = (uint32_t*)take(4ull * n_dgrams + 4);
-  w.total = (uint32_t*)take(8);
-  w.attempts = (uint32_t*)take(8);
-  w.keys = (uint32_t*)take(4ull * max_pkts);
-  w.vals = (uint32_t*)take(4ull * max_pkts);
-  w.skeys = (uint32_t*)take(4ull * max_pkts);
-  w.svals = (uint32_t*)take(4ull * max_pkts);
-  w.shist = (uint32_t*)take(4ull * kSortDigits * sort_blocks(max_pkts));
-  w.tkeys = (uint32_t*)take(4ull * max_pkts);
-  w.tvals = (uint32_t*)take(4ull * max_pkts);
-  w.seg_lo = (uint32_t*)take(4ull * n_conns);
-  w.seg_hi = (uint32_t*)take(4ull * n_conns);
+  Carve c(p);
+  w.counts = c.take<uint32_t>((size_t)n_dgrams + 1);
+  w.base = c.take<uint32_t>((size_t)n_dgrams + 1);
+  w.total = c.take<uint32_t>(2);
+  w.attempts = c.take<uint32_t>(2);
+  w.keys = c.take<uint32_t>(max_pkts);
+  w.vals = c.take<uint32_t>(max_pkts);
+  w.skeys = c.take<uint32_t>(max_pkts);
+  w.svals = c.take<uint32_t>(max_pkts);
+  w.shist = c.take<uint32_t>((size_t)kSortDigits * sort_blocks(max_pkts));
+  w.tkeys = c.take<uint32_t>(max_pkts);
+  w.tvals = c.take<uint32_t>(max_pkts);
+  w.seg_lo = c.take<uint32_t>(n_conns);
+  w.seg_hi = c.take<uint32_t>(n_conns);
   const size_t max_segs = (size_t)n_conns + ((size_t)max_pkts + 63) / 64;  // segments of >= 64 packets
-  w.vstate = (uint32_t*)take(8ull * n_conns + 8);
-  w.segend = (SegState*)take(2 * sizeof(SegState) * max_segs);  // this walk's and the previous walk's
+  w.vstate = c.take<uint32_t>(2 * ((size_t)n_conns + 1));
+  w.segend = c.take<SegState>(2 * max_segs);  // this walk's and the previous walk's
   w.max_segs = (uint32_t)max_segs;
-  w.conn0 = (mq_conn_recv*)take(sizeof(mq_conn_recv) * (size_t)n_conns);
-  w.work = (RecvWork*)take(sizeof(RecvWork) * (size_t)max_pkts);
-  w.work_s = (RecvWork*)take(sizeof(RecvWork) * (size_t)max_pkts);
-  w.hdr_s = (RecvPlan*)take(sizeof(RecvPlan) * (size_t)max_pkts);
-  w.tried = (RecvPlan*)take(sizeof(RecvPlan) * (size_t)max_pkts);
-  w.tried2 = (RecvPlan*)take(sizeof(RecvPlan) * (size_t)max_pkts);
-  w.hpm = (uint2*)take(8ull * max_pkts);
-  w.d1 = (mq_pkt_desc*)take(sizeof(mq_pkt_desc) * (size_t)max_pkts);
-  w.d2 = (mq_pkt_desc*)take(sizeof(mq_pkt_desc) * (size_t)max_pkts);
-  w.st1 = take(max_pkts);
-  w.st2 = take(max_pkts);
-  w.outcome = take(max_pkts);
+  w.conn0 = c.take<mq_conn_recv>(n_conns);
+  w.work = c.take<RecvWork>(max_pkts);
+  w.work_s = c.take<RecvWork>(max_pkts);
+  w.hdr_s = c.take<RecvPlan>(max_pkts);
+  w.tried = c.take<RecvPlan>(max_pkts);
+  w.tried2 = c.take<RecvPlan>(max_pkts);
+  w.hpm = c.take<uint2>(max_pkts);
+  w.d1 = c.take<mq_pkt_desc>(max_pkts);
+  w.d2 = c.take<mq_pkt_desc>(max_pkts);
+  w.st1 = c.take<uint8_t>(max_pkts);
+  w.st2 = c.take<uint8_t>(max_pkts);
+  w.outcome = c.take<uint8_t>(max_pkts);
   w.cub_bytes = cub_bytes(n_dgrams, max_pkts);
-  w.cub = take(w.cub_bytes);
-  w.open_ws = take(open_ws_bytes);
-  w.bytes = o;
+  w.cub = c.take<uint8_t>(w.cub_bytes);
+  w.open_ws = c.take<uint8_t>(open_ws_bytes);
+  w.bytes = c.bytes();
   return w;
 }
 }  // namespace

@@ -31,10 +31,8 @@
 // written once), so first[slot] is the lowest datagram index of that tag; flags, ranks and with them
 // every output follow from the inputs. Only the positions of the new table entries depend on timing,
 // and no result depends on those.
-#include <hipcub/hipcub.hpp>
-
-#include "mq_device.h"
 #include "mq_launch.h"
+#include "mq_replay.h"
 #include "mq_route.h"
 
 namespace mq {
@@ -59,9 +57,6 @@ struct RouteWs {
 constexpr uint8_t kRoutePending = 0x80;  // status of an admissible miss between the kernels of one call
 
 // ---- wave helpers ------------------------------------------------------------------------------------
-__device__ __forceinline__ uint32_t lanes_below(uint64_t m) {  // set bits of m below this lane
-  return __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
-}
 __device__ __forceinline__ uint32_t wave_sum(uint32_t x) {  // every lane of the wave must call it
 #pragma unroll
   for (int o = 32; o; o >>= 1) x += __shfl_xor(x, o);
@@ -365,46 +360,32 @@ extern "C" __global__ __launch_bounds__(256) void mq_cid_rehash_kernel(const Cid
 
 // ---- host side -----------------------------------------------------------------------------------------
 namespace {
-size_t al256(size_t b) { return (b + 255) & ~(size_t)255; }
 uint32_t route_set_slots(uint32_t n) {  // a power of two >= 2n (n <= 2^31 - 1 gives at most 2^32: see below)
   uint64_t s = 16;
   while (s < 2ull * n) s <<= 1;
   return (uint32_t)(s - 1);  // as a mask
 }
-size_t route_cub_bytes(uint32_t n) {
-  size_t b = 0;
-  (void)hipcub::DeviceScan::ExclusiveSum(nullptr, b, (const uint32_t*)nullptr, (uint32_t*)nullptr, (int)n + 1);
-  return b;
-}
-// workspace: [head][keys][sidx][flags][rank][set][first][scan scratch]
-size_t route_layout(uint32_t n, void* base, RouteWs* w) {
-  const uint32_t mask = route_set_slots(n);
-  size_t off = 0;
-  auto take = [&](size_t bytes) {
-    const size_t at = off;
-    off += al256(bytes);
-    return base ? (uint8_t*)base + at : nullptr;
-  };
-  uint8_t* head = take(sizeof(RouteHead));
-  uint8_t* keys = take(sizeof(CidSlot) * (size_t)n);
-  uint8_t* sidx = take(4 * (size_t)n);
-  uint8_t* flags = take(4 * ((size_t)n + 1));
-  uint8_t* rank = take(4 * ((size_t)n + 1));
-  uint8_t* set = take(8 * ((size_t)mask + 1));
-  uint8_t* first = take(4 * ((size_t)mask + 1));
-  const size_t cb = route_cub_bytes(n);
-  uint8_t* cub = take(cb);
-  if (w) {
-    w->head = (RouteHead*)head, w->keys = (CidSlot*)keys, w->sidx = (uint32_t*)sidx, w->flags = (uint32_t*)flags;
-    w->rank = (uint32_t*)rank, w->set = (unsigned long long*)set, w->first = (uint32_t*)first, w->set_mask = mask;
-    w->cub = cub, w->cub_bytes = cb;
-  }
-  return off;
+size_t route_layout(uint32_t n, void* base, RouteWs& w) {
+  Carve c(base);
+  w.set_mask = route_set_slots(n);
+  w.head = c.take<RouteHead>(1);
+  w.keys = c.take<CidSlot>(n);
+  w.sidx = c.take<uint32_t>(n);
+  w.flags = c.take<uint32_t>((size_t)n + 1);
+  w.rank = c.take<uint32_t>((size_t)n + 1);
+  w.set = c.take<unsigned long long>((size_t)w.set_mask + 1);
+  w.first = c.take<uint32_t>((size_t)w.set_mask + 1);
+  w.cub_bytes = cub_temp_bytes<false>(0, 0, {n + 1});
+  w.cub = c.take<uint8_t>(w.cub_bytes);
+  return c.bytes();
 }
 dim3 grid_for(uint64_t lanes) { return dim3((uint32_t)((lanes + 255) / 256)); }
 }  // namespace
 
-size_t mq_route_workspace(uint32_t n) { return route_layout(n, nullptr, nullptr); }
+size_t mq_route_workspace(uint32_t n) {
+  RouteWs w = {};
+  return route_layout(n, nullptr, w);
+}
 
 hipError_t mq_launch_route(const CidTableDev& t, const uint8_t* arena, uint64_t arena_len, mq_dgram* dg, uint32_t n,
                            uint32_t sdl, const mq_route_admit* admit, uint8_t* status, void* workspace,
@@ -418,7 +399,7 @@ hipError_t mq_launch_route(const CidTableDev& t, const uint8_t* arena, uint64_t 
     return hipGetLastError();
   }
   if (n) {
-    route_layout(n, workspace, &w);
+    route_layout(n, workspace, w);
     // the batch set: all-ones = empty; first[]: all-ones = no datagram yet
     if ((e = hipMemsetAsync(w.set, 0xFF, 8 * ((size_t)w.set_mask + 1), s)) != hipSuccess) return e;
     if ((e = hipMemsetAsync(w.first, 0xFF, 4 * ((size_t)w.set_mask + 1), s)) != hipSuccess) return e;
@@ -426,8 +407,7 @@ hipError_t mq_launch_route(const CidTableDev& t, const uint8_t* arena, uint64_t 
                        admit->min_initial_len, status, w);
     hipLaunchKernelGGL(mq_route_groups_kernel, grid_for(n), dim3(256), 0, s, t, n, admit->max_new, status, w);
     if ((e = hipGetLastError()) != hipSuccess) return e;
-    size_t cb = w.cub_bytes;
-    if ((e = hipcub::DeviceScan::ExclusiveSum(w.cub, cb, w.flags, w.rank, (int)n + 1, s)) != hipSuccess) return e;
+    if ((e = exclusive_sum(w, w.flags, w.rank, n + 1, s)) != hipSuccess) return e;
   }
   const uint64_t lanes = n > admit->max_new ? n : admit->max_new;
   hipLaunchKernelGGL(mq_route_admit_kernel, grid_for(lanes ? lanes : 1), dim3(256), 0, s, t, dg, n, sdl, admit->conns,

@@ -24,10 +24,8 @@
 // mq_batch_stream_read: mark (a request's claim word becomes "free"), claim (atomicMin of the request
 // index on the claim word of its buffer), serve (the winner answers and copies with the same routine).
 // The claim's minimum does not depend on arrival order, so every output is a function of the inputs.
-#include <hipcub/hipcub.hpp>
-
-#include "mq_device.h"
 #include "mq_launch.h"
+#include "mq_replay.h"
 #include "mq_stream_data.h"
 
 #ifndef MQ_STREAM_COPY_LANES
@@ -49,8 +47,7 @@ static_assert(sizeof(mq_stream_entry) == 48 && sizeof(mq_stream_buf) == 32 && si
               "ABI");
 static_assert(MQ_STREAM_SLOTS == kStreamSlots && MQ_STREAM_WOULD_BLOCK == kStreamWouldBlock, "ABI constants");
 
-struct StreamDataWs {
-  uint32_t *keys_in, *keys, *idx_in, *idx;  // max_frames each
+struct StreamDataWs : SortWs {              // max_frames each
   uint32_t *flags, *pos;                    // max_frames + 1: selected, their exclusive scan
   uint64_t* src;                            // max_frames: arena offset of a selected STREAM record's data
   void* cub;
@@ -61,17 +58,7 @@ struct StreamReadWs {
   uint32_t* slot;   // n_reqs: 0..31, kStreamNone, or kReadInvalid
 };
 constexpr uint32_t kReadInvalid = 0xFE;
-
-// ---- the group's 32 lanes (as in mq_acks.hip) -------------------------------------------------------
-__device__ __forceinline__ uint32_t sd_ballot(bool p, uint32_t group_first) {
-  return (uint32_t)(__builtin_amdgcn_ballot_w64(p) >> group_first);
-}
-__device__ __forceinline__ uint32_t sd_get32(uint32_t v, uint32_t src) {
-  return (uint32_t)__shfl((int)v, (int)(src & 31u), (int)kSdGroup);
-}
-__device__ __forceinline__ uint64_t sd_get64(uint64_t v, uint32_t src) {
-  return sd_get32((uint32_t)v, src) | (uint64_t)sd_get32((uint32_t)(v >> 32), src) << 32;
-}
+using SdLanes = LaneGroup<kSdGroup>;
 
 // ---- the copy routine: n bytes, any alignment on both sides, nothing outside [dst, dst + n) written ----
 template <uint32_t kLanes>
@@ -130,70 +117,46 @@ __device__ __forceinline__ void sd_store_buf(mq_stream_buf* p, const StreamBuf& 
 using namespace mq;
 
 // select: which records are processed, for which connection, and where their data starts
-__global__ __launch_bounds__(kSdBlock) void mq_stream_select_kernel(
-    uint64_t arena_len, const mq_recv_pkt* __restrict__ pkts, const uint32_t* __restrict__ n_pkts_dev, uint32_t max_pkts,
-    const mq_dgram* __restrict__ dgrams, uint32_t n_dgrams, const mq_frame* __restrict__ frames,
-    const uint32_t* __restrict__ n_frames_dev, uint32_t max_frames, uint32_t n_conns, StreamDataWs ws) {
+__global__ __launch_bounds__(kSdBlock) void mq_stream_select_kernel(StreamDataArgs a, StreamDataWs ws) {
   const uint32_t k = blockIdx.x * kSdBlock + threadIdx.x;
-  if (k > max_frames) return;
-  if (k == max_frames) {
+  if (k > a.max_frames) return;
+  if (k == a.max_frames) {
     ws.flags[k] = 0;
     return;
   }
-  const uint32_t nf = *n_frames_dev, np = *n_pkts_dev;
-  const uint32_t n_frames = nf < max_frames ? nf : max_frames, n_pkts = np < max_pkts ? np : max_pkts;
-  uint32_t key = n_conns;
+  const uint32_t nf = *a.n_frames_dev, np = *a.n_pkts_dev;
+  const uint32_t n_frames = nf < a.max_frames ? nf : a.max_frames, n_pkts = np < a.max_pkts ? np : a.max_pkts;
+  uint32_t key = a.n_conns;
   uint64_t src = 0;
   if (k < n_frames) {
-    const uint4 f = reinterpret_cast<const uint4*>(frames + k)[0];  // pkt; pos, len; type, level, data_pos; data_len, aux
+    const uint4 f = reinterpret_cast<const uint4*>(a.frames + k)[0];  // pkt; pos, len; type, level, data_pos; data_len, aux
     const uint32_t type = f.z & 0xFFu, data_pos = f.z >> 16, data_len = f.w & 0xFFFFu;
-    if ((type == 0x04 || (type >= 0x08 && type <= 0x0f)) && f.x < n_pkts) {
-      const uint4 a = reinterpret_cast<const uint4*>(pkts + f.x)[0];  // offset, pn
-      const uint4 b = reinterpret_cast<const uint4*>(pkts + f.x)[1];  // len, dgram, payload_offset + level + status, ..
-      if (b.y < n_dgrams) {
-        const uint32_t c = dgrams[b.y].conn;
-        const uint64_t off = a.x | (uint64_t)a.y << 32;
-        const uint32_t rel = (b.z & 0xFFFFu) + data_pos;
-        src = off + rel;
-        // no wrap: the sum is compared piece by piece
-        const bool inside =
-            type == 0x04 || (off <= arena_len && rel <= arena_len - off && data_len <= arena_len - off - rel);
-        if (c < n_conns && inside) key = c;
-      }
+    if (type == 0x04 || (type >= 0x08 && type <= 0x0f)) {
+      const FrameSite site =
+          frame_site(a.pkts, n_pkts, a.dgrams, a.n_dgrams, a.arena_len, f.x, data_pos, data_len, type != 0x04);
+      src = site.src;
+      if (site.conn < a.n_conns && site.inside) key = site.conn;
     }
   }
   ws.keys_in[k] = key;
   ws.idx_in[k] = k;
-  ws.flags[k] = key < n_conns;
+  ws.flags[k] = key < a.n_conns;
   ws.src[k] = src;
 }
 
-// replay: every connection's selected records, in record order
+// replay: every connection's selected records, in record order. Its arguments stay a flat __restrict__ list:
+// with the argument struct the replay over 64 long connections measured 1.3 % slower
 __global__ __launch_bounds__(kSdBlock) void mq_stream_replay_kernel(
     const mq_frame* __restrict__ frames, uint32_t max_frames, mq_conn_streams* __restrict__ streams, uint32_t n_conns,
     uint32_t stream_buf, uint64_t initial_max, uint32_t call_flags, mq_stream_evt* __restrict__ evts,
     uint32_t* __restrict__ n_evts, StreamDataWs ws) {
   const uint32_t c = blockIdx.x * kSdGroupsPerBlock + threadIdx.x / kSdGroup;
-  const uint32_t lane = threadIdx.x & (kSdGroup - 1);
-  const uint32_t group_first = threadIdx.x & (kWave - 1) & ~(kSdGroup - 1);
+  const uint32_t lane = SdLanes::lane();
+  const uint32_t group_first = SdLanes::first();
   const bool is_client = (call_flags & MQ_STREAMS_CLIENT) != 0;
   if (blockIdx.x == 0 && threadIdx.x == 0) *n_evts = ws.pos[max_frames];
   uint32_t r = 0, r_end = 0;
-  if (c < n_conns) {  // the connection's run: [lower bound of c, lower bound of c + 1) in the ascending keys
-    uint32_t lo = 0, hi = max_frames;
-    while (lo < hi) {
-      const uint32_t mid = lo + (hi - lo) / 2;
-      if (ws.keys[mid] < c) lo = mid + 1;
-      else hi = mid;
-    }
-    r = lo, hi = max_frames;
-    while (lo < hi) {
-      const uint32_t mid = lo + (hi - lo) / 2;
-      if (ws.keys[mid] <= c) lo = mid + 1;
-      else hi = mid;
-    }
-    r_end = lo;
-  }
+  if (c < n_conns) key_run(ws.keys, max_frames, c, r, r_end);  // the connection's run
   const bool touched = r < r_end;
   StreamEntry e = {};
   StreamBuf b = {};
@@ -223,14 +186,14 @@ __global__ __launch_bounds__(kSdBlock) void mq_stream_replay_kernel(
     for (uint32_t j = 0; j < kSdGroup; ++j) {
       const bool on = j < cnt;
       if (__builtin_amdgcn_ballot_w64(on) == 0) break;  // the longer chunk of the wave's two groups
-      const uint32_t k = sd_get32(my_k, j), type = sd_get32(my_type, j), len = sd_get32(my_len, j);
-      const uint32_t pos = sd_get32(my_pos, j);
-      const uint64_t id = sd_get64(my_id, j), a = sd_get64(my_a, j), src = sd_get64(my_src, j);
+      const uint32_t k = SdLanes::get32(my_k, j), type = SdLanes::get32(my_type, j), len = SdLanes::get32(my_len, j);
+      const uint32_t pos = SdLanes::get32(my_pos, j);
+      const uint64_t id = SdLanes::get64(my_id, j), a = SdLanes::get64(my_a, j), src = SdLanes::get64(my_src, j);
       const bool is_stream = type >= 0x08, fin = (type & 1u) != 0;
       const bool m_used = (e.flags & kSeUsed) != 0;
-      const uint32_t m_found = sd_ballot(on && m_used && e.id == id, group_first);
-      const uint32_t m_free = sd_ballot(on && !m_used, group_first);
-      const uint32_t b_found = sd_ballot(on && b.used && b.stream_id == id, group_first);
+      const uint32_t m_found = SdLanes::ballot(on && m_used && e.id == id, group_first);
+      const uint32_t m_free = SdLanes::ballot(on && !m_used, group_first);
+      const uint32_t b_found = SdLanes::ballot(on && b.used && b.stream_id == id, group_first);
       uint32_t mslot = kStreamNone, bslot = kStreamNone, ev_flags = 0;
       if (m_found) {
         mslot = (uint32_t)__builtin_ctz(m_found);
@@ -244,12 +207,12 @@ __global__ __launch_bounds__(kSdBlock) void mq_stream_replay_kernel(
       const bool have = on && mslot != kStreamNone;
       uint32_t mark_l = 0xFF;
       if (have && lane == mslot) mark_l = is_stream ? stream_mark_recv(e, a, len, fin) : stream_handle_reset(e, a);
-      const uint32_t mark_got = sd_get32(mark_l, mslot);
+      const uint32_t mark_got = SdLanes::get32(mark_l, mslot);
       const uint32_t mark = have ? mark_got : 0xFFu;
       if (have) ev_flags |= is_stream ? kEvReadable : kEvReset;
       // store_stream_data
       const bool storing = have && is_stream;
-      const uint32_t b_free = sd_ballot(on && !b.used, group_first);
+      const uint32_t b_free = SdLanes::ballot(on && !b.used, group_first);
       uint32_t store = kStoreNone;
       if (storing) {
         if (b_found) {
@@ -269,7 +232,7 @@ __global__ __launch_bounds__(kSdBlock) void mq_stream_replay_kernel(
         pack_l = s.store | (uint32_t)s.flags << 8 | (uint32_t)s.skip << 16;
         n_l = s.copy_len, dst_l = s.dst;
       }
-      const uint32_t pack = sd_get32(pack_l, bslot), n = sd_get32(n_l, bslot), dst = sd_get32(dst_l, bslot);
+      const uint32_t pack = SdLanes::get32(pack_l, bslot), n = SdLanes::get32(n_l, bslot), dst = SdLanes::get32(dst_l, bslot);
       if (on && lane == 0) {
         uint32_t skip = 0, copy_len = 0, at = 0;
         uint64_t from = 0;
@@ -309,20 +272,16 @@ __global__ __launch_bounds__(kSdBlock) void mq_stream_copy_kernel(const uint8_t*
 
 // ---- mq_batch_stream_read -----------------------------------------------------------------------------
 // mark: which buffer a request names; its claim word becomes "free"
-__global__ __launch_bounds__(kSdBlock) void mq_stream_read_mark_kernel(const mq_conn_streams* __restrict__ streams,
-                                                                       uint32_t n_conns,
-                                                                       const mq_stream_read_req* __restrict__ reqs,
-                                                                       uint32_t n_reqs, uint64_t out_len,
-                                                                       StreamReadWs ws) {
+__global__ __launch_bounds__(kSdBlock) void mq_stream_read_mark_kernel(StreamReadArgs args, StreamReadWs ws) {
   const uint32_t k = blockIdx.x * kSdBlock + threadIdx.x;
-  if (k >= n_reqs) return;
-  const uint4 a = reinterpret_cast<const uint4*>(reqs + k)[0];  // conn, cap, stream_id
-  const uint64_t id = a.z | (uint64_t)a.w << 32, out_offset = reqs[k].out_offset;
+  if (k >= args.n_reqs) return;
+  const uint4 a = reinterpret_cast<const uint4*>(args.reqs + k)[0];  // conn, cap, stream_id
+  const uint64_t id = a.z | (uint64_t)a.w << 32, out_offset = args.reqs[k].out_offset;
   uint32_t slot = kReadInvalid;
-  if (a.x < n_conns && out_offset <= out_len && a.y <= out_len - out_offset) {
+  if (a.x < args.n_conns && out_offset <= args.out_len && a.y <= args.out_len - out_offset) {
     slot = kStreamNone;
     for (uint32_t s = 0; s < kStreamSlots; ++s) {
-      const mq_stream_buf* p = &streams[a.x].buf[s];
+      const mq_stream_buf* p = &args.streams[a.x].buf[s];
       if (p->used && p->stream_id == id) {
         slot = s;
         break;
@@ -343,18 +302,12 @@ __global__ __launch_bounds__(kSdBlock) void mq_stream_read_claim_kernel(const mq
 }
 
 // serve: kCopyLanes lanes per request
-__global__ __launch_bounds__(kSdBlock) void mq_stream_read_serve_kernel(mq_conn_streams* __restrict__ streams,
-                                                                        const uint8_t* __restrict__ bufs,
-                                                                        uint32_t stream_buf,
-                                                                        const mq_stream_read_req* __restrict__ reqs,
-                                                                        uint32_t n_reqs, uint8_t* __restrict__ out,
-                                                                        mq_stream_read_res* __restrict__ res,
-                                                                        StreamReadWs ws) {
+__global__ __launch_bounds__(kSdBlock) void mq_stream_read_serve_kernel(StreamReadArgs args, StreamReadWs ws) {
   const uint64_t k = ((uint64_t)blockIdx.x * kSdBlock + threadIdx.x) / kCopyLanes;
-  if (k >= n_reqs) return;
+  if (k >= args.n_reqs) return;
   const uint32_t lane = threadIdx.x & (kCopyLanes - 1);
   const uint32_t slot = ws.slot[k];
-  const uint4 a = reinterpret_cast<const uint4*>(reqs + k)[0];
+  const uint4 a = reinterpret_cast<const uint4*>(args.reqs + k)[0];
   uint32_t status = MQ_OK, copied = 0, fin = 0;
   if (slot == kReadInvalid) {
     status = MQ_ERR_INVALID_ARG;
@@ -363,115 +316,86 @@ __global__ __launch_bounds__(kSdBlock) void mq_stream_read_serve_kernel(mq_conn_
   } else if (ws.claim[(uint64_t)a.x * kStreamSlots + slot] != (uint32_t)k) {
     status = MQ_ERR_DEFERRED;
   } else {
-    mq_stream_buf* p = &streams[a.x].buf[slot];
+    mq_stream_buf* p = &args.streams[a.x].buf[slot];
     StreamBuf b;
-    sd_load_buf(p, b, stream_buf);  // every lane of the request holds the header before lane 0 writes it
+    sd_load_buf(p, b, args.stream_buf);  // every lane of the request holds the header before lane 0 writes it
     const StreamRead r = stream_read(b, a.y);
     status = r.status, copied = r.copied, fin = r.fin;
     if (copied) {
-      sd_copy<kCopyLanes>(out + reqs[k].out_offset, bufs + ((uint64_t)a.x * kStreamSlots + slot) * stream_buf + r.from,
-                          copied, lane);
+      sd_copy<kCopyLanes>(args.out + args.reqs[k].out_offset,
+                          args.bufs + ((uint64_t)a.x * kStreamSlots + slot) * args.stream_buf + r.from, copied, lane);
     }
     if (lane == 0 && status == MQ_OK) p->len = b.len, p->read_offset = b.read_offset, p->used = b.used;
   }
   if (lane == 0) {
     const uint32_t s = slot < kStreamSlots ? slot : kStreamNone;
-    *reinterpret_cast<uint2*>(res + k) = make_uint2(copied, status | fin << 8 | s << 16);
+    *reinterpret_cast<uint2*>(args.res + k) = make_uint2(copied, status | fin << 8 | s << 16);
   }
 }
 
 // ---- host side -----------------------------------------------------------------------------------------
 namespace {
-size_t sd_al256(size_t b) { return (b + 255) & ~(size_t)255; }
-uint32_t sd_key_bits(uint32_t n_conns) {  // the keys are 0 .. n_conns
-  uint32_t bits = 1;
-  while (bits < 32 && ((uint64_t)n_conns >> bits)) ++bits;
-  return bits;
+size_t stream_data_layout(uint32_t n, uint32_t n_conns, void* base, StreamDataWs& w) {
+  Carve c(base);
+  w.keys_in = c.take<uint32_t>(n);
+  w.keys = c.take<uint32_t>(n);
+  w.idx_in = c.take<uint32_t>(n);
+  w.idx = c.take<uint32_t>(n);
+  w.flags = c.take<uint32_t>((size_t)n + 1);
+  w.pos = c.take<uint32_t>((size_t)n + 1);
+  w.src = c.take<uint64_t>(n);
+  w.cub_bytes = cub_temp_bytes<true>(n, key_bits(n_conns), {n + 1});
+  w.cub = c.take<uint8_t>(w.cub_bytes);
+  return c.bytes();  // no slack behind the last piece, unlike stream read
 }
-size_t sd_cub_bytes(uint32_t max_frames, uint32_t n_conns) {
-  size_t a = 0, b = 0;
-  (void)hipcub::DeviceRadixSort::SortPairs(nullptr, a, (const uint32_t*)nullptr, (uint32_t*)nullptr,
-                                           (const uint32_t*)nullptr, (uint32_t*)nullptr, (int)max_frames, 0,
-                                           (int)sd_key_bits(n_conns));
-  (void)hipcub::DeviceScan::ExclusiveSum(nullptr, b, (const uint32_t*)nullptr, (uint32_t*)nullptr, (int)max_frames + 1);
-  return a > b ? a : b;
-}
-size_t stream_data_layout(uint32_t n, uint32_t n_conns, void* base, StreamDataWs* w) {
-  size_t off = 0;
-  auto take = [&](size_t bytes) {
-    const size_t at = off;
-    off += sd_al256(bytes);
-    return base ? (uint8_t*)base + at : nullptr;
-  };
-  uint8_t* p[7];
-  for (int q = 0; q < 4; ++q) p[q] = take(4 * (size_t)n);
-  p[4] = take(4 * ((size_t)n + 1));
-  p[5] = take(4 * ((size_t)n + 1));
-  p[6] = take(8 * (size_t)n);
-  const size_t cb = sd_cub_bytes(n, n_conns);
-  uint8_t* cub = take(cb);
-  if (w) {
-    w->keys_in = (uint32_t*)p[0], w->keys = (uint32_t*)p[1], w->idx_in = (uint32_t*)p[2], w->idx = (uint32_t*)p[3];
-    w->flags = (uint32_t*)p[4], w->pos = (uint32_t*)p[5], w->src = (uint64_t*)p[6];
-    w->cub = cub, w->cub_bytes = cb;
-  }
-  return off;
-}
-size_t stream_read_layout(uint32_t n_reqs, uint32_t n_conns, void* base, StreamReadWs* w) {
-  const size_t claim = sd_al256(4 * (size_t)kStreamSlots * n_conns), slot = sd_al256(4 * (size_t)n_reqs);
-  if (w) w->claim = (uint32_t*)base, w->slot = (uint32_t*)((uint8_t*)base + claim);
-  return claim + slot + 256;
+size_t stream_read_layout(uint32_t n_reqs, uint32_t n_conns, void* base, StreamReadWs& w) {
+  Carve c(base);
+  w.claim = c.take<uint32_t>((size_t)kStreamSlots * n_conns);
+  w.slot = c.take<uint32_t>(n_reqs);
+  // 256 bytes that no kernel touches. Nobody knows why they are there; callers size by this figure
+  return c.bytes() + 256;
 }
 dim3 sd_blocks(uint64_t threads) { return dim3((uint32_t)((threads + kSdBlock - 1) / kSdBlock)); }
 }  // namespace
 
 size_t mq_stream_data_workspace(uint32_t max_frames, uint32_t n_conns) {
-  return stream_data_layout(max_frames, n_conns, nullptr, nullptr);
+  StreamDataWs w = {};
+  return stream_data_layout(max_frames, n_conns, nullptr, w);
 }
 size_t mq_stream_read_workspace(uint32_t n_reqs, uint32_t n_conns) {
-  return stream_read_layout(n_reqs, n_conns, nullptr, nullptr);
+  StreamReadWs w = {};
+  return stream_read_layout(n_reqs, n_conns, nullptr, w);
 }
 
-hipError_t mq_launch_stream_data(const uint8_t* arena, uint64_t arena_len, const mq_recv_pkt* pkts,
-                                 const uint32_t* n_pkts_dev, uint32_t max_pkts, const mq_dgram* dgrams,
-                                 uint32_t n_dgrams, const mq_frame* frames, const uint32_t* n_frames_dev,
-                                 uint32_t max_frames, mq_conn_streams* streams, uint32_t n_conns, uint8_t* bufs,
-                                 uint32_t stream_buf, uint64_t initial_max_stream_data, uint32_t flags,
-                                 mq_stream_evt* evts, uint32_t* n_evts, void* workspace, hipStream_t s) {
+// max_frames > 0 and n_conns > 0
+hipError_t mq_launch_stream_data(const StreamDataArgs& a, void* workspace, hipStream_t s) {
   StreamDataWs w = {};
-  stream_data_layout(max_frames, n_conns, workspace, &w);
+  stream_data_layout(a.max_frames, a.n_conns, workspace, w);
   hipError_t e;
   const dim3 block(kSdBlock);
-  hipLaunchKernelGGL(mq_stream_select_kernel, sd_blocks((uint64_t)max_frames + 1), block, 0, s, arena_len, pkts,
-                     n_pkts_dev, max_pkts, dgrams, n_dgrams, frames, n_frames_dev, max_frames, n_conns, w);
+  hipLaunchKernelGGL(mq_stream_select_kernel, sd_blocks((uint64_t)a.max_frames + 1), block, 0, s, a, w);
   if ((e = hipGetLastError()) != hipSuccess) return e;
-  size_t cb = w.cub_bytes;
-  if ((e = hipcub::DeviceScan::ExclusiveSum(w.cub, cb, w.flags, w.pos, (int)max_frames + 1, s)) != hipSuccess) return e;
-  cb = w.cub_bytes;
-  if ((e = hipcub::DeviceRadixSort::SortPairs(w.cub, cb, w.keys_in, w.keys, w.idx_in, w.idx, (int)max_frames, 0,
-                                              (int)sd_key_bits(n_conns), s)) != hipSuccess)
-    return e;
-  hipLaunchKernelGGL(mq_stream_replay_kernel, sd_blocks((uint64_t)n_conns * kSdGroup), block, 0, s, frames, max_frames,
-                     streams, n_conns, stream_buf, initial_max_stream_data, flags, evts, n_evts, w);
+  if ((e = exclusive_sum(w, w.flags, w.pos, a.max_frames + 1, s)) != hipSuccess) return e;
+  if ((e = sort_by_key(w, a.max_frames, key_bits(a.n_conns), s)) != hipSuccess) return e;
+  hipLaunchKernelGGL(mq_stream_replay_kernel, sd_blocks((uint64_t)a.n_conns * kSdGroup), block, 0, s, a.frames,
+                     a.max_frames, a.streams, a.n_conns, a.stream_buf, a.initial_max_stream_data, a.flags, a.evts, a.n_evts,
+                     w);
   if ((e = hipGetLastError()) != hipSuccess) return e;
-  hipLaunchKernelGGL(mq_stream_copy_kernel, sd_blocks((uint64_t)max_frames * kCopyLanes), block, 0, s, arena, evts,
-                     max_frames, bufs, stream_buf, w);
+  hipLaunchKernelGGL(mq_stream_copy_kernel, sd_blocks((uint64_t)a.max_frames * kCopyLanes), block, 0, s, a.arena, a.evts,
+                     a.max_frames, a.bufs, a.stream_buf, w);
   return hipGetLastError();
 }
 
-hipError_t mq_launch_stream_read(mq_conn_streams* streams, uint32_t n_conns, const uint8_t* bufs, uint32_t stream_buf,
-                                 const mq_stream_read_req* reqs, uint32_t n_reqs, uint8_t* out, uint64_t out_len,
-                                 mq_stream_read_res* res, void* workspace, hipStream_t s) {
+// n_reqs > 0
+hipError_t mq_launch_stream_read(const StreamReadArgs& a, void* workspace, hipStream_t s) {
   StreamReadWs w = {};
-  stream_read_layout(n_reqs, n_conns, workspace, &w);
+  stream_read_layout(a.n_reqs, a.n_conns, workspace, w);
   hipError_t e;
   const dim3 block(kSdBlock);
-  hipLaunchKernelGGL(mq_stream_read_mark_kernel, sd_blocks(n_reqs), block, 0, s, streams, n_conns, reqs, n_reqs, out_len,
-                     w);
+  hipLaunchKernelGGL(mq_stream_read_mark_kernel, sd_blocks(a.n_reqs), block, 0, s, a, w);
   if ((e = hipGetLastError()) != hipSuccess) return e;
-  hipLaunchKernelGGL(mq_stream_read_claim_kernel, sd_blocks(n_reqs), block, 0, s, reqs, n_reqs, w);
+  hipLaunchKernelGGL(mq_stream_read_claim_kernel, sd_blocks(a.n_reqs), block, 0, s, a.reqs, a.n_reqs, w);
   if ((e = hipGetLastError()) != hipSuccess) return e;
-  hipLaunchKernelGGL(mq_stream_read_serve_kernel, sd_blocks((uint64_t)n_reqs * kCopyLanes), block, 0, s, streams, bufs,
-                     stream_buf, reqs, n_reqs, out, res, w);
+  hipLaunchKernelGGL(mq_stream_read_serve_kernel, sd_blocks((uint64_t)a.n_reqs * kCopyLanes), block, 0, s, a, w);
   return hipGetLastError();
 }
